@@ -1,6 +1,8 @@
 """bench.py — StylEx G+D+enc train-step throughput on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps K --warmup W              # one GPU
+    python bench.py --gpus 1 --steps K --warmup W --full       # + roofline, Bench A, fp32 mode, CPU baseline
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + DIR/<name>.npy of the last timed step
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" = one ``Trainer.train()`` call = one D optimiser step + one G optimiser step over
@@ -10,11 +12,16 @@ batches, 32 images per GPU per micro-batch, GAE=2 with alternating training => o
 encoder micro-step per phase; steps start at 0 so one call in four carries the gradient penalty.
 Inputs are device-resident before the timed region.  images/s counts B*GAE images per call.
 
-Prints ONE JSON line (rank 0) with the contract keys plus
+Prints ONE JSON line (rank 0) with the contract keys.  A plain run sets up, warms up, times the K steps, writes the
+outputs of the last timed step if `--dump-outputs DIR` is given, and prints the line.  With `--full` the line carries,
+each from runs of its own after the timed steps,
   roofline     — dominant conv KERNEL (rocprofv3 name), algorithmic FLOPs / hipEvent time, vs the dense MFMA peak;
                  its kernel class, the per-kernel table and the per-layer mixed roofline beside it
+  frozen_nets  — the frozen classifier / LPIPS share of a step, part by part (N=1 only)
+  bench_a      — the same shapes at gradient_accumulate_every = 1 (N=1 only)
   fp32_parity_mode — the same workload in the exact-fp32 mode (images/s, fraction of the fp32 MFMA peak)
   cpu_baseline — the CPU oracle ("port") timed on the host cores on a bounded sample (N=1 only)
+and null in their place otherwise.
 """
 import argparse
 import json
@@ -339,6 +346,26 @@ def cpu_baseline(args):
                       % (args.image_size, bs, args.gae, t_gp, t_plain)}
 
 
+DUMP_MAX_VALUES = 1 << 22  # per network: 4 networks x 16 MB of float32 at most
+
+
+def dump_outputs(tr, out_dir):
+    """What a caller of Trainer.train() receives after the last timed step: the loss scalars it publishes (float64; an
+    unset one is NaN) and the trained parameters of G, S, encoder and D, each network's parameters flattened in
+    parameters() order as float32.  A network with more than DUMP_MAX_VALUES values is written as a sample at fixed
+    seeded positions, the same on every run of the same configuration."""
+    os.makedirs(out_dir, exist_ok=True)
+    losses = [tr.d_loss, tr.g_loss, tr.total_rec_loss, tr.total_kl_loss, tr.last_gp_loss]
+    np.save(os.path.join(out_dir, "losses.npy"),
+            np.array([float("nan") if v is None else float(v) for v in losses], dtype=np.float64))
+    for name in ("G", "S", "encoder", "D"):
+        flat = torch.cat([p.detach().reshape(-1).float() for p in getattr(tr.StylEx, name).parameters()])
+        if flat.numel() > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(1234).choice(flat.numel(), DUMP_MAX_VALUES, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy())
+
+
 def main(argv=None, backend="nccl", device=None):
     """`backend` / `device` are overridden only by tests/test_ddp_gloo.py (2 ranks over gloo on the CPU test double): the
     N > 1 plumbing below — barrier, MAX-reduce of the elapsed time, rank-0-only JSON line, process-group teardown — is
@@ -355,19 +382,19 @@ def main(argv=None, backend="nccl", device=None):
     ap.add_argument("--network-capacity", type=int, default=16)
     ap.add_argument("--fmap-max", type=int, default=512)
     ap.add_argument("--workdir", default="/tmp/stylex_bench")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--miopen-find", action="store_true",
                     help="let MIOpen search its algorithms for the frozen classifier / LPIPS during the warm-up "
                          "(cudnn.benchmark; default: immediate mode, the reference's cli.py:38 setting and the Trainer's)")
     ap.add_argument("--no-miopen-find", action="store_true", help="(default since round 4; accepted for old scripts)")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-threads", type=int, default=16)
-    ap.add_argument("--roofline-steps", type=int, default=4)
+    ap.add_argument("--roofline-steps", type=int, default=4, help="instrumented steps of the roofline record (--full)")
     ap.add_argument("--per-layer-top", type=int, default=14, help="rows of roofline.per_layer.layers (0 = every layer)")
     ap.add_argument("--fp32-steps", type=int, default=4,
-                    help="timed train() calls of the fp32 parity mode for the fp32_parity_mode sub-record (0 = skip)")
+                    help="timed train() calls of the fp32 parity mode for the fp32_parity_mode sub-record (--full; 0 = skip)")
     ap.add_argument("--bench-a-steps", type=int, default=12,
-                    help="timed train() calls of Bench A (GAE = 1) for the bench_a sub-record (0 = skip; N = 1 only)")
+                    help="timed train() calls of Bench A (GAE = 1) for the bench_a sub-record (--full; 0 = skip; N = 1 only)")
     ap.add_argument("--graphs", type=int, default=int(os.environ.get("STYLEX_GRAPHS", "0")),
                     help="1 = replay the step as captured HIP graphs after the eager warm-up calls (0 = eager enqueue, "
                          "the default: at 256 px the step is GPU-bound and the capture of the multi-stream step is not "
@@ -386,6 +413,12 @@ def main(argv=None, backend="nccl", device=None):
     ap.add_argument("--host-share", type=int, default=int(os.environ.get("STYLEX_HOST_SHARE", "1")),
                     help="emulate the host share of one rank on an N-GPU node: pin this process (before anything touches "
                          "the GPU; no re-exec) to 1/N of the cores it may run on")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the sub-records (roofline, frozen_nets, bench_a, "
+                         "fp32_parity_mode, cpu_baseline; each takes runs of its own); a plain run reports them as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss scalars, trained G / S / encoder / D parameters, "
+                         "a fixed seeded sample of the larger ones) as DIR/<name>.npy")
     args = ap.parse_args(argv)
     if args.host_share > 1:
         cores = sorted(os.sched_getaffinity(0))
@@ -429,6 +462,11 @@ def main(argv=None, backend="nccl", device=None):
     # search unsafe on this stack (head of stylex/hip_backend.py).  --miopen-find restores the search.
     os.environ["STYLEX_MIOPEN_BENCHMARK"] = "1" if args.miopen_find else "0"
     torch.backends.cudnn.benchmark = bool(args.miopen_find)
+    # ... and restricted to its deterministic algorithms, as cli.py's set_seed does by default (reference cli.py:37).
+    # Every kernel of the HIP path is run-to-run reproducible; MIOpen's default algorithms for the frozen networks are
+    # not (tools/determinism_check.py), and the untrained GAN amplifies their last-bit differences within a few steps.
+    # Pinned, two runs with the same arguments compute the same steps (what --dump-outputs writes).
+    torch.backends.cudnn.deterministic = True
     tr = build_trainer(args, device, rank, world)
 
     def sync():
@@ -460,10 +498,12 @@ def main(argv=None, backend="nccl", device=None):
         dt = float(t.item())
     images = world * args.batch * args.gae * args.steps
     value = images / dt
+    if args.dump_outputs and rank == 0:  # before anything below trains the same Trainer further
+        dump_outputs(tr, args.dump_outputs)
 
     # ---- roofline of the dominant conv kernel class, hipEvent-timed on the launch stream
     roof = None
-    if args.roofline_steps > 0:  # on EVERY rank: train() contains the gradient all-reduce collectives
+    if args.full and args.roofline_steps > 0:  # on EVERY rank: train() contains the gradient all-reduce collectives
         # kernel quality is measured with the branch-level stream concurrency of the Trainer switched off, so that an
         # event pair brackets one kernel class running alone (the timed region above runs with it on)
         prev_streams = os.environ.get("STYLEX_STREAMS")
@@ -487,7 +527,7 @@ def main(argv=None, backend="nccl", device=None):
             os.environ["STYLEX_STREAMS"] = prev_streams
         # forward and data-gradient launches run the SAME kernels (LDS-halo / implicit-GEMM conv with swapped
         # roles), so they form one kernel class; the weight gradient has its own kernels
-    if args.roofline_steps > 0 and rank == 0:
+    if args.full and args.roofline_steps > 0 and rank == 0:
         merged = {"fwd_bwd_data": {k: rep["fwd"][k] + rep["bwd_data"][k] for k in ("ms", "flops", "launches", "bytes")},
                   "bwd_weight": rep["bwd_weight"]}
         name, r = max(merged.items(), key=lambda kv: kv[1]["ms"])
@@ -543,26 +583,26 @@ def main(argv=None, backend="nccl", device=None):
 
     # ---- the frozen networks' share, part by part, and Bench A (N = 1 only)
     frozen_rec = bench_a = None
-    if rank == 0 and world == 1 and args.roofline_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.roofline_steps > 0:
         frozen_rec = frozen_split(args, tr, device)
-    if rank == 0 and world == 1 and args.bench_a_steps > 0 and args.gae != 1:
+    if args.full and rank == 0 and world == 1 and args.bench_a_steps > 0 and args.gae != 1:
         bench_a = bench_a_record(args, device)
 
     # ---- the fp32 parity mode on the same workload (N = 1 only): images/s and the class fraction of the fp32 MFMA peak
     fp32_rec = None
-    if rank == 0 and world == 1 and args.fp32_steps > 0 and args.precision != "fp32":
+    if args.full and rank == 0 and world == 1 and args.fp32_steps > 0 and args.precision != "fp32":
         fp32_rec = fp32_record(args, device, tr)
         tr = None
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if rank == 0:
         gf = algorithmic_gflop_per_image(args.gae, args.image_size, args.network_capacity, args.fmap_max)
         line = {
             "metric": "StylEx G+D+enc train-step images/sec @%dpx" % args.image_size, "value": round(value, 2), "unit": "images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full, "ms_per_step": round(dt / args.steps * 1e3, 2),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision,
             "data": "synthetic (torch.rand 256x256 batches resident in HBM, random-init weights, seeded "
                     "random-weight ResNet-18 classifier and LPIPS-AlexNet)",
@@ -577,7 +617,8 @@ def main(argv=None, backend="nccl", device=None):
                        "rng": ("latents / noise planes drawn on the GPU generator (as every rank of the data-parallel path; "
                                "--device-rng 0 = the reference's CPU draws + upload: -3 %, profiles/r06_d_ab_imagegrad_devrng.txt)")
                               if args.device_rng else "CPU generator draws + upload (reference order)",
-                       "frozen_nets": ("classifier forward: stock MIOpen fp32, immediate mode (north_star; reference cli.py:38); in the bf16 "
+                       "frozen_nets": ("classifier forward: stock MIOpen fp32, immediate mode, deterministic algorithms (north_star; reference "
+                                       "cli.py:37-38); in the bf16 "
                                        "mode its data gradient and LPIPS-AlexNet's layers 2-5 run on this library's bf16 kernels "
                                        "(frozen_resnet._ResNetBodyHybrid, lpips_alex._taps_bf16; STYLEX_FROZEN_BWD_BF16=0 / "
                                        "STYLEX_LPIPS_BF16=0: all on MIOpen fp32), outside the roofline classes")

@@ -94,3 +94,27 @@ def test_two_processes_sharing_the_gpu_stay_bit_identical():
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "two_processes_one_gpu.txt"), "w") as f:
         f.write("parameter checksums of the two processes: %r (equal: %s)\n" % (per_proc, per_proc[0] == per_proc[1]))
+
+
+@pytest.mark.timeout(900)
+def test_bench_py_dumps_are_identical_run_to_run(tmp_path):
+    """bench.py at its own size and settings, run twice in fresh processes with the same arguments (the timed steps start
+    on a gradient-penalty step): every array --dump-outputs writes is bit-identical between the two runs."""
+    import subprocess
+
+    import numpy as np
+
+    dirs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--workdir", str(tmp_path / "work"), "--dump-outputs", str(d)], cwd=ROOT, capture_output=True,
+                           text=True, timeout=400)
+        assert r.returncode == 0, r.stderr[-3000:]
+        dirs.append(d)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and "losses.npy" in names, names
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype == b.dtype and a.shape == b.shape, n
+        assert np.array_equal(a, b, equal_nan=True), (n, float(np.nanmax(np.abs(a.astype(np.float64) - b))))

@@ -2655,7 +2655,7 @@ def test_bench_py_two_ranks_on_one_gpu():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "bench_two_ranks_one_gpu.py"), "--steps", "3", "--warmup", "2",
-                        "--bench-a-steps", "0", "--fp32-steps", "0", "--roofline-steps", "1"], capture_output=True, text=True,
+                        "--bench-a-steps", "0", "--fp32-steps", "0", "--roofline-steps", "1", "--full"], capture_output=True, text=True,
                        timeout=800, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

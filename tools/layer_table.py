@@ -9,7 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 small = "--small" in sys.argv
 args = [a for a in sys.argv[1:] if a != "--small"]
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--bench-a-steps", "0", "--fp32-steps", "0",
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--bench-a-steps", "0", "--fp32-steps", "0",
                       "--steps", "2", "--warmup", "2", "--per-layer-top", "0"] + args, capture_output=True, text=True).stdout
 line = [l for l in out.splitlines() if l.startswith("{")][-1]
 j = json.loads(line)
