@@ -36,6 +36,8 @@ def _prefix_states(G, w_tensor, noise):
     for li, block in enumerate(G.blocks):
         istyle = w_tensor[:, li]
         s1, s2 = block.to_style1(istyle), block.to_style2(istyle)
+        if G.attns[li] is not None:  # attn_layers: the attention block sits on the block's input
+            x = G.attns[li](x)
         states.append((x, rgb, s1, s2))
         x, _ = block.forward_main(x, istyle, noise, styles=(s1, s2))
         rgb = block.to_rgb(x, rgb, istyle)
@@ -51,6 +53,8 @@ def _suffix(G, k, x, rgb, w_tensor, noise, styles_k):
     rgb = None if rgb is None else rgb.expand(p, -1, -1, -1)
     for li in range(k, len(G.blocks)):
         block = G.blocks[li]
+        if li > k and G.attns[li] is not None:  # block k's own attention is already in its prefix state
+            x = G.attns[li](x)
         x, _ = block.forward_main(x, w[:, li], nz, styles=styles_k if li == k else None)
         rgb = block.to_rgb(x, rgb, w[:, li])
     return rgb.float()
@@ -225,6 +229,8 @@ def change_images(G, classifier, dlatents, sindex, style_direction_index, s_styl
                 s2 = s2.clone()
                 s2[:, widx - block.input_channels] += delta
             styles = (s1, s2)
+        if G.attns[li] is not None:
+            x = G.attns[li](x)
         x, _ = block.forward_main(x, w, noise, styles=styles)
         rgb = block.to_rgb(x, rgb, w)
     changed = rgb.float()

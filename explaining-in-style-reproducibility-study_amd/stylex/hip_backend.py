@@ -157,6 +157,16 @@ SIGNATURES = {
                                             ctypes.c_void_p]),
     "stylex_l1_mean_bwd": (ctypes.c_int, [_c_f] * 5 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, _i64p, _i64p, _i64p,
                                             ctypes.c_void_p]),
+    "stylex_linattn_chunks": (ctypes.c_int, [_i64p]),
+    "stylex_linattn_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, _c_f, _c_f, _c_f, _c_f, _c_f, _i64p, ctypes.c_int,
+                                          ctypes.c_void_p]),
+    "stylex_linattn_bwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p] + [_c_f] * 8 + [_i64p, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_chan_norm_fwd": (ctypes.c_int, [_c_f] * 6 + [_i64p, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_chan_norm_bwd_blocks": (ctypes.c_int, [_i64p]),
+    "stylex_chan_norm_bwd": (ctypes.c_int, [_c_f] * 8 + [_i64p, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_dwconv3x3_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_dwconv3x3_wgrad_blocks": (ctypes.c_int, [_i64p]),
+    "stylex_dwconv3x3_bwd_weight": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_void_p]),
     "stylex_timing_report": (ctypes.c_int, [ctypes.c_int, _i64p, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }
@@ -1784,3 +1794,127 @@ def timing_layers(cap=512):
     return [dict(cls=names[meta[r * 10]], B=meta[r * 10 + 1], H=meta[r * 10 + 2], W=meta[r * 10 + 3], C=meta[r * 10 + 4],
                  N=meta[r * 10 + 5], k=meta[r * 10 + 6], stride=meta[r * 10 + 7], s2d=meta[r * 10 + 8],
                  launches=meta[r * 10 + 9], ms=vals[r * 3], flops=vals[r * 3 + 1], bytes=vals[r * 3 + 2]) for r in range(n)]
+
+
+# ---- linear-attention blocks of attn_layers (csrc/linattn.hip) ------------------------------------------------------
+
+def _pow2_lanes(c):
+    """C = 4 << s, s in [0, 6]: the C / 4 lanes of a pixel fit one wave."""
+    return c in (4, 8, 16, 32, 64, 128, 256)
+
+
+def chan_norm_supported(c):
+    return _pow2_lanes(c)
+
+
+def dwconv3x3_supported(c):
+    return _pow2_lanes(c)
+
+
+def linattn_supported(c, heads):
+    return heads > 0 and c == 64 * heads
+
+
+def chan_norm_fwd(x, g, b, eps):
+    """ChanNorm over the channels of NHWC x; returns (y, mean[P], std[P]) — the statistics feed chan_norm_bwd."""
+    lib = _ensure_device(x)
+    assert is_cl(x)
+    bsz, c, h, w = x.shape
+    p = bsz * h * w
+    y = empty_cl(tuple(x.shape), x)
+    mean = _empty(p, dtype=torch.float32, device=x.device)
+    std = _empty(p, dtype=torch.float32, device=x.device)
+    _check(lib.stylex_chan_norm_fwd(_ptr(x), _ptr(_f32(g)), _ptr(_f32(b)), _ptr(y), _ptr(mean), _ptr(std), _shape(p, c),
+                                    float(eps), _adt(x), _stream()), "stylex_chan_norm_fwd")
+    return y, mean, std
+
+
+def chan_norm_bwd(x, gy, g, mean, std, eps, want_params=True):
+    """(gx, dg[C], db[C]) of chan_norm_fwd; dg / db are None without want_params."""
+    lib = _ensure_device(x)
+    assert is_cl(x) and is_cl(gy) and x.dtype == gy.dtype and x.shape == gy.shape
+    bsz, c, h, w = x.shape
+    sh = _shape(bsz * h * w, c)
+    gx = empty_cl(tuple(x.shape), x)
+    partial = dgb = None
+    if want_params:
+        partial = _empty(lib.stylex_chan_norm_bwd_blocks(sh) * 2 * c, dtype=torch.float32, device=x.device)
+        dgb = _empty(2, c, dtype=torch.float32, device=x.device)
+    _check(lib.stylex_chan_norm_bwd(_ptr(x), _ptr(gy), _ptr(_f32(g)), _ptr(mean), _ptr(std), _ptr(gx), _ptr(partial), _ptr(dgb),
+                                    sh, float(eps), _adt(x), _stream()), "stylex_chan_norm_bwd")
+    return (gx, dgb[0], dgb[1]) if want_params else (gx, None, None)
+
+
+def dwconv3x3_fwd(x, w):
+    """Depthwise 3x3 / pad 1 of NHWC x with w [C, 1, 3, 3] (fp32)."""
+    lib = _ensure_device(x)
+    assert is_cl(x) and tuple(w.shape) == (x.shape[1], 1, 3, 3)
+    bsz, c, h, wd = x.shape
+    y = empty_cl(tuple(x.shape), x)
+    _check(lib.stylex_dwconv3x3_fwd(_ptr(x), _ptr(_f32(w)), _ptr(y), _shape(bsz, h, wd, c), _adt(x), _stream()),
+           "stylex_dwconv3x3_fwd")
+    return y
+
+
+def dwconv3x3_bwd_weight(x, gy):
+    """dw[C, 1, 3, 3] (fp32) = sum over batch and pixels of x[p + tap] * gy[p]."""
+    lib = _ensure_device(x)
+    assert is_cl(x) and is_cl(gy) and x.dtype == gy.dtype and x.shape == gy.shape
+    bsz, c, h, wd = x.shape
+    sh = _shape(bsz, h, wd, c)
+    partial = _empty(lib.stylex_dwconv3x3_wgrad_blocks(sh) * c * 9, dtype=torch.float32, device=x.device)
+    dw = _empty(c, 1, 3, 3, dtype=torch.float32, device=x.device)
+    _check(lib.stylex_dwconv3x3_bwd_weight(_ptr(x), _ptr(gy), _ptr(partial), _ptr(dw), sh, _adt(x), _stream()),
+           "stylex_dwconv3x3_bwd_weight")
+    return dw
+
+
+def _nhwc_view(t):
+    """A tensor the attention kernels can address in place: channel stride 1, one stride from pixel to pixel within a
+    sample (a channel slice of an NHWC tensor qualifies); anything else is copied to dense NHWC.  Returns the tensor and
+    its pixel / sample strides in elements."""
+    b, c, h, w = t.shape
+    sb, sc, sh_, sw = t.stride()
+    px = sw if w > 1 else (sh_ if h > 1 else c)  # strides of size-1 dimensions carry no information
+    ok = (sc == 1 and px % 4 == 0 and px >= c and (h == 1 or w == 1 or sh_ == w * sw)
+          and (b == 1 or (sb % 4 == 0 and sb >= h * w * px)) and t.data_ptr() % (4 * t.element_size()) == 0)
+    if not ok:
+        t = t.contiguous(memory_format=torch.channels_last)
+        px, sb = c, h * w * c
+    return t, px, (sb if b > 1 else h * w * px)
+
+
+def _linattn_args(q, k, v, heads):
+    assert q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype and q.shape[1] == 64 * heads
+    (q, qp, qb), (k, kp, kb), (v, vp, vb) = _nhwc_view(q), _nhwc_view(k), _nhwc_view(v)
+    b, c, h, w = q.shape
+    return q, k, v, _shape(qp, qb, kp, kb, vp, vb), _shape(b, h * w, heads)
+
+
+def linattn_fwd(q, k, v, heads):
+    """Attention core (see include/stylex_hip.h): returns (y, pre-GELU values, context [B, heads, 64, 64], lse [B, heads, 64])."""
+    lib = _ensure_device(q)
+    q, k, v, strides, sh = _linattn_args(q, k, v, heads)
+    b = q.shape[0]
+    nch = lib.stylex_linattn_chunks(sh)
+    y, pre = empty_cl(tuple(q.shape), q), empty_cl(tuple(q.shape), q)
+    context = _empty(b, heads, 64, 64, dtype=torch.float32, device=q.device)
+    lse = _empty(b, heads, 64, dtype=torch.float32, device=q.device)
+    ws = _empty(b * heads * nch * (64 * 64 + 128), dtype=torch.float32, device=q.device)
+    _check(lib.stylex_linattn_fwd(_ptr(q), _ptr(k), _ptr(v), strides, _ptr(y), _ptr(pre), _ptr(context), _ptr(lse), _ptr(ws),
+                                  sh, _adt(q), _stream()), "stylex_linattn_fwd")
+    return y, pre, context, lse
+
+
+def linattn_bwd(q, k, v, pre, context, lse, gy, heads):
+    """(dq, dk, dv) of linattn_fwd, each dense NHWC."""
+    lib = _ensure_device(q)
+    q, k, v, strides, sh = _linattn_args(q, k, v, heads)
+    assert is_cl(gy) and is_cl(pre) and gy.dtype == q.dtype and gy.shape == q.shape
+    b = q.shape[0]
+    nch = lib.stylex_linattn_chunks(sh)
+    dq, dk, dv = (empty_cl(tuple(q.shape), q) for _ in range(3))
+    ws = _empty(b * heads * (nch + 1) * 64 * 64 + b * heads * 64, dtype=torch.float32, device=q.device)
+    _check(lib.stylex_linattn_bwd(_ptr(q), _ptr(k), _ptr(v), strides, _ptr(pre), _ptr(gy), _ptr(context), _ptr(lse), _ptr(dq),
+                                  _ptr(dk), _ptr(dv), _ptr(ws), sh, _adt(q), _stream()), "stylex_linattn_bwd")
+    return dq, dk, dv

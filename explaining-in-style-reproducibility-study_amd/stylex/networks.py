@@ -84,8 +84,8 @@ class HipConv2d(nn.Conv2d):
     """nn.Conv2d parameter container (same init, same keys) running on the implicit-GEMM kernel.
     ``act=True`` fuses the LeakyReLU(0.2) that follows it in the reference's nn.Sequential."""
 
-    def __init__(self, cin, cout, k, padding=0, stride=1, act=False):
-        super().__init__(cin, cout, k, padding=padding, stride=stride)
+    def __init__(self, cin, cout, k, padding=0, stride=1, act=False, bias=True):
+        super().__init__(cin, cout, k, padding=padding, stride=stride, bias=bias)
         self.act = act
 
     def forward(self, x):
@@ -98,6 +98,100 @@ class _FusedAct(nn.Module):
 
     def forward(self, x):
         return x
+
+
+# ---- linear-attention blocks (attn_layers; reference :100-206) --------------------------------------------------------
+# Constructor shapes, attribute names and creation order are what the checkpoint format and the seeded init fix; the
+# forwards are written against ops (ChanNorm / depthwise 3x3 / attention core kernels, the dense 1x1 convs on the
+# existing conv entry points).
+
+
+class Residual(nn.Module):
+    def __init__(self, fn):
+        super().__init__()
+        self.fn = fn
+
+    def forward(self, x):
+        fused = getattr(self.fn, "forward_plus", None)
+        if fused is not None:  # the branch's last 1x1 conv adds x in its epilogue: one kernel and one rounding fewer
+            return fused(x, x)
+        return self.fn(x) + x
+
+
+class ChanNorm(nn.Module):
+    def __init__(self, dim, eps=1e-5):
+        super().__init__()
+        self.eps = eps
+        self.g = nn.Parameter(torch.ones(1, dim, 1, 1))
+        self.b = nn.Parameter(torch.zeros(1, dim, 1, 1))
+
+    def forward(self, x):
+        return ops.chan_norm(x, self.g, self.b, self.eps)
+
+
+class PreNorm(nn.Module):
+    def __init__(self, dim, fn):
+        super().__init__()
+        self.fn = fn
+        self.norm = ChanNorm(dim)
+
+    def forward(self, x):
+        return self.fn(self.norm(x))
+
+    def forward_plus(self, x, residual):
+        """fn(norm(x)) + residual, the sum taken in the epilogue of fn's last conv (ops.conv2d(..., residual=))."""
+        y = self.norm(x)
+        if isinstance(self.fn, LinearAttention):
+            return self.fn(y, residual=residual)
+        first, last = self.fn[0], self.fn[-1]  # the feed-forward branch: conv1x1 + LeakyReLU (fused), conv1x1
+        return ops.conv2d(first(y), last.weight, last.bias, residual=residual, res_scale=1.0)
+
+
+class HipDepthwiseConv3x3(nn.Conv2d):
+    """nn.Conv2d(dim, dim, 3, padding=1, groups=dim, bias=False) parameter container on ops.depthwise_conv3x3."""
+
+    def __init__(self, dim):
+        super().__init__(dim, dim, 3, padding=1, groups=dim, bias=False)
+
+    def forward(self, x):
+        return ops.depthwise_conv3x3(x, self.weight)
+
+
+class DepthWiseConv2d(nn.Module):
+    def __init__(self, dim_in, dim_out, kernel_size, padding=0, stride=1, bias=True):
+        super().__init__()
+        assert kernel_size == 3 and padding == 1 and stride == 1 and not bias, "only the form LinearAttention uses"
+        self.net = nn.Sequential(HipDepthwiseConv3x3(dim_in), HipConv2d(dim_in, dim_out, 1, bias=False))
+
+    def forward(self, x):
+        return self.net(x)
+
+
+class LinearAttention(nn.Module):
+    def __init__(self, dim, dim_head=64, heads=8):
+        super().__init__()
+        self.scale = dim_head ** -0.5
+        self.heads = heads
+        inner_dim = dim_head * heads
+        self.nonlin = nn.GELU()  # applied inside ops.linear_attention_core
+        self.to_q = HipConv2d(dim, inner_dim, 1, bias=False)
+        self.to_kv = DepthWiseConv2d(dim, inner_dim * 2, 3, padding=1, bias=False)
+        self.to_out = HipConv2d(inner_dim, dim, 1)
+
+    def forward(self, fmap, residual=None):
+        q = self.to_q(fmap)
+        k, v = self.to_kv(fmap).chunk(2, dim=1)
+        out = ops.linear_attention_core(q, k, v, self.heads)
+        if residual is None:
+            return self.to_out(out)
+        return ops.conv2d(out, self.to_out.weight, self.to_out.bias, residual=residual, res_scale=1.0)
+
+
+def attn_and_ff(chan):
+    """One layer of linear self-attention and a 1x1-conv feed-forward, both pre-normed residual blocks."""
+    return nn.Sequential(
+        Residual(PreNorm(chan, LinearAttention(chan))),
+        Residual(PreNorm(chan, nn.Sequential(HipConv2d(chan, chan * 2, 1, act=True), _FusedAct(), HipConv2d(chan * 2, chan, 1)))))
 
 
 class EqualLinear(nn.Module):  # reference :576-587
@@ -269,7 +363,7 @@ class Generator(nn.Module):  # reference :747-825
     def __init__(self, image_size, latent_dim, network_capacity=16, transparent=False, attn_layers=[], no_const=False,
                  fmap_max=512):
         super().__init__()
-        assert not attn_layers and not no_const, "attention / no_const variants are out of scope (SURVEY §2a)"
+        assert not no_const, "the no_const variant is out of scope (SURVEY §2a)"
         self.image_size, self.latent_dim = image_size, latent_dim
         self.num_layers = int(log2(image_size) - 1)
         filters = generator_filters(image_size, network_capacity, fmap_max)
@@ -279,7 +373,8 @@ class Generator(nn.Module):  # reference :747-825
         self.blocks = nn.ModuleList([])
         self.attns = nn.ModuleList([])
         for ind in range(self.num_layers):
-            self.attns.append(None)
+            # attention sits on the INPUT of block `ind` (reference :780); built before the block: RNG order
+            self.attns.append(attn_and_ff(filters[ind]) if self.num_layers - ind in attn_layers else None)
             self.blocks.append(GeneratorBlock(latent_dim, filters[ind], filters[ind + 1], upsample=ind != 0,
                                               upsample_rgb=ind != self.num_layers - 1, rgba=transparent))
 
@@ -294,6 +389,8 @@ class Generator(nn.Module):  # reference :747-825
         # pairwise by the engine): ~20 fewer launches per generator backward.
         per_layer = styles.unbind(1)
         for li, block in enumerate(self.blocks):
+            if exists(self.attns[li]):
+                x = self.attns[li](x)
             x, sc = block.forward_main(x, per_layer[li], input_noise)
             coords.append(sc)
             rgb = block.to_rgb(x, rgb, per_layer[li], style=block.__dict__.pop("_rgb_style", None), padded=True)
@@ -309,12 +406,15 @@ class DiscriminatorE(nn.Module):  # reference :842-909 (D: 1 logit; encoder: enc
     def __init__(self, image_size, network_capacity=16, fq_layers=[], fq_dict_size=256, attn_layers=[],
                  transparent=False, encoder=False, encoder_dim=512, fmap_max=512, conditional=False):
         super().__init__()
-        assert not fq_layers and not attn_layers, "fq / attention variants are out of scope (SURVEY §2a)"
+        assert not fq_layers, "the fq variant is out of scope (SURVEY §2a)"
         filters = discriminator_filters(image_size, network_capacity, fmap_max, transparent)
         n = len(filters) - 1
-        self.blocks = nn.ModuleList([DiscriminatorBlock(filters[i], filters[i + 1], downsample=i != n - 1)
-                                     for i in range(n)])
-        self.attn_blocks = nn.ModuleList([None] * n)
+        blocks, attn_blocks = [], []
+        for i in range(n):  # block, then the attention on its OUTPUT (reference :864-869): RNG order
+            blocks.append(DiscriminatorBlock(filters[i], filters[i + 1], downsample=i != n - 1))
+            attn_blocks.append(attn_and_ff(filters[i + 1]) if i + 1 in attn_layers else None)
+        self.blocks = nn.ModuleList(blocks)
+        self.attn_blocks = nn.ModuleList(attn_blocks)
         self.quantize_blocks = nn.ModuleList([None] * n)
         chan_last = filters[-1]
         self.final_conv = HipConv2d(chan_last, chan_last, 3, padding=1)
@@ -327,8 +427,10 @@ class DiscriminatorE(nn.Module):  # reference :842-909 (D: 1 logit; encoder: enc
         self.fc = nn.Linear(2 * 2 * chan_last, encoder_dim if encoder else (2 if self.conditional else 1))
 
     def forward(self, x, probabilities=None):
-        for block in self.blocks:
+        for block, attn in zip(self.blocks, self.attn_blocks):
             x = block(x)
+            if exists(attn):
+                x = attn(x)
         x = self.final_conv(x)
         x = self.fc(self.flatten(x).float())
         if self.conditional:

@@ -1425,3 +1425,171 @@ def residual_merge(x, res):
 
 def rowwise_sumsq(x2d):
     return _IMPL.rowwise_sumsq(x2d)
+
+
+# ------------------------------------------------------------------------------------------
+# linear-attention blocks (attn_layers; reference stylex/stylex_train.py:100-206): ChanNorm, the depthwise 3x3 of
+# to_kv and the attention core.  Each op has a COMPOSABLE path (the reference's formula in plain torch ops: CPU
+# tensors, shapes the kernels do not cover, and every pass that is differentiated twice) and a FUSED path
+# (csrc/linattn.hip) for CUDA tensors.  These three do not go through the implementation object: on CPU tensors they
+# never touch hip_backend, so the CPU suite runs them as they are.
+# ------------------------------------------------------------------------------------------
+
+_ATTN_FUSED = os.environ.get("STYLEX_ATTN_FUSED", "1") != "0"
+
+
+def set_attn_fused(flag):
+    """False: CUDA tensors take the composable (ATen) path too — the baseline of tools/bench_attn.py."""
+    global _ATTN_FUSED
+    prev = _ATTN_FUSED
+    _ATTN_FUSED = bool(flag)
+    return prev
+
+
+def _wide(t):
+    """fp32 working precision for the composable formulas (bf16 activations are widened; fp32 / fp64 stay)."""
+    return t.float() if t.dtype in (torch.bfloat16, torch.float16) else t
+
+
+def _narrow(y, like):
+    """Result dtype of a composable op: the activation dtype on the GPU, the input's own dtype on the CPU."""
+    if like.is_cuda:
+        return _act(y)
+    return y if y.dtype == like.dtype else y.to(like.dtype)
+
+
+def _chan_norm_composable(x, g, b, eps):
+    x = _wide(x)
+    mean = x.mean(dim=1, keepdim=True)
+    std = x.var(dim=1, unbiased=False, keepdim=True).sqrt()
+    return (x - mean) / (std + eps) * g + b  # eps joins the standard deviation, not the variance
+
+
+def _depthwise_composable(x, w):
+    return F.conv2d(_wide(x), w, None, stride=1, padding=1, groups=w.shape[0])
+
+
+def _linattn_composable(q, k, v, heads):
+    b, c, h, w = q.shape
+    d, n = c // heads, h * w
+    q, k, v = (_wide(t).reshape(b, heads, d, n) for t in (q, k, v))
+    q = q.softmax(dim=2) * d ** -0.5  # over the channels of a head, per pixel
+    k = k.softmax(dim=3)  # over the pixels, per (sample, head, channel)
+    context = torch.matmul(k, v.transpose(2, 3))  # [b, heads, d, e]
+    out = torch.matmul(context.transpose(2, 3), q)  # [b, heads, e, n]
+    return F.gelu(out.reshape(b, c, h, w))  # exact (erf) GELU
+
+
+def _second_order_grads(ctx, fn, inputs, n_data, gy):
+    """Backward of a fused Function while the backward pass itself is being recorded (create_graph=True: gradient
+    penalty, path length): the composable formula is re-evaluated on the saved inputs and differentiated by autograd,
+    so the returned gradients carry a graph.  inputs[:n_data] are activations, the rest parameters."""
+    idx = [i for i in range(len(inputs))
+           if ctx.needs_input_grad[i] and inputs[i].requires_grad and (i < n_data or not _INPUTS_ONLY)]
+    out = [None] * len(inputs)
+    if idx:
+        with torch.enable_grad():
+            y = fn(*inputs)
+            grads = torch.autograd.grad(y, [inputs[i] for i in idx], gy.to(y.dtype), create_graph=True, allow_unused=True)
+        for i, g in zip(idx, grads):
+            out[i] = g
+    return out
+
+
+class _ChanNormFused(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, g, b, eps):
+        y, mean, std = hb.chan_norm_fwd(_cl(x), g, b, eps)
+        ctx.save_for_backward(x, g, b, mean, std)
+        ctx.eps = eps
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, g, b, mean, std = ctx.saved_tensors
+        eps = ctx.eps
+        if torch.is_grad_enabled():
+            return (*_second_order_grads(ctx, lambda x_, g_, b_: _act(_chan_norm_composable(x_, g_, b_, eps)), (x, g, b), 1, gy),
+                    None)
+        want_p = (_want_param_grad(ctx, 1) or _want_param_grad(ctx, 2))
+        gx, dg, db = hb.chan_norm_bwd(_cl(x), _cl(gy), g, mean, std, eps, want_params=want_p)
+        return (gx if ctx.needs_input_grad[0] else None, dg.view_as(g) if want_p and ctx.needs_input_grad[1] else None,
+                db.view_as(b) if want_p and ctx.needs_input_grad[2] else None, None)
+
+
+class _DWConv(torch.autograd.Function):
+    """Depthwise 3x3 / pad 1.  Closed under differentiation like the dense triad above:
+    DW(x, w) --bwd--> DW(gy, flip w), DWW(x, gy);   DWW(x, gy) --bwd--> DW(gy, flip ggw), DW(x, ggw)."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        x = _cl(x)
+        ctx.save_for_backward(x, w)
+        return hb.dwconv3x3_fwd(x, w)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gx = _DWConv.apply(gy, w.flip(2, 3)) if ctx.needs_input_grad[0] else None
+        gw = _DWWgrad.apply(x, gy) if _want_param_grad(ctx, 1) else None
+        return gx, gw
+
+
+class _DWWgrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gy):
+        x, gy = _cl(x), _cl(gy)
+        ctx.save_for_backward(x, gy)
+        return hb.dwconv3x3_bwd_weight(x, gy)
+
+    @staticmethod
+    def backward(ctx, ggw):
+        x, gy = ctx.saved_tensors
+        ggw = ggw.contiguous()
+        d_x = _DWConv.apply(gy, ggw.flip(2, 3)) if ctx.needs_input_grad[0] else None
+        d_gy = _DWConv.apply(x, ggw) if ctx.needs_input_grad[1] else None
+        return d_x, d_gy
+
+
+class _LinAttnFused(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, heads):
+        y, pre, context, lse = hb.linattn_fwd(q, k, v, heads)
+        ctx.save_for_backward(q, k, v, pre, context, lse)
+        ctx.heads = heads
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        q, k, v, pre, context, lse = ctx.saved_tensors
+        heads = ctx.heads
+        if torch.is_grad_enabled():
+            return (*_second_order_grads(ctx, lambda q_, k_, v_: _act(_linattn_composable(q_, k_, v_, heads)), (q, k, v), 3, gy),
+                    None)
+        dq, dk, dv = hb.linattn_bwd(q, k, v, pre, context, lse, _cl(gy), heads)
+        return dq, dk, dv, None
+
+
+def _attn_fused(x):
+    return x.is_cuda and _ATTN_FUSED
+
+
+def chan_norm(x, g, b, eps=1e-5):
+    """ChanNorm: per pixel over the channels, (x - mean) / (sqrt(biased var) + eps) * g + b; g, b: [1, C, 1, 1]."""
+    if _attn_fused(x) and hb.chan_norm_supported(x.shape[1]):
+        return _ChanNormFused.apply(_act(x), g, b, float(eps))
+    return _narrow(_chan_norm_composable(x, g, b, eps), x)
+
+
+def depthwise_conv3x3(x, weight):
+    """nn.Conv2d(C, C, 3, padding=1, groups=C, bias=False); weight: [C, 1, 3, 3]."""
+    if _attn_fused(x) and hb.dwconv3x3_supported(x.shape[1]):
+        return _DWConv.apply(_act(x), weight)
+    return _narrow(_depthwise_composable(x, weight), x)
+
+
+def linear_attention_core(q, k, v, heads):
+    """gelu(softmax_channels(q) * d^-0.5 @ (softmax_pixels(k)^T @ v)) per (sample, head); q, k, v: [B, heads * d, H, W]."""
+    if _attn_fused(q) and hb.linattn_supported(q.shape[1], heads):
+        return _LinAttnFused.apply(_act(q), _act(k), _act(v), int(heads))
+    return _narrow(_linattn_composable(q, k, v, heads), q)

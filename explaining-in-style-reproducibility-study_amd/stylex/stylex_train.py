@@ -1350,8 +1350,10 @@ class Trainer:
     def _graphs_enabled(self):
         """Whole-step HIP graphs: opt-in with Trainer(graphs=True) / STYLEX_GRAPHS=1 (bench.py turns them on).  A step
         is ~1100 kernel launches issued through ctypes/ATen (~70 ms of host time per step); captured once
-        per step shape (with / without the gradient penalty) it replays with one hipGraphLaunch."""
-        return self.graphs and self.device.type == "cuda"
+        per step shape (with / without the gradient penalty) it replays with one hipGraphLaunch.
+        Refused with attn_layers: the attention blocks have not been captured or checked under replay, the step then
+        runs eagerly."""
+        return self.graphs and self.device.type == "cuda" and not self.attn_layers
 
     def _opt_step(self, opt):
         """Optimiser step + invalidation of the cached operand copies of the weights it changed (bf16 GEMM layouts,

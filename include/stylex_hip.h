@@ -490,6 +490,40 @@ int stylex_l1_mean_fwd(const void* a, const void* b, float* partial, float* out,
 int stylex_l1_mean_bwd(const void* a, const void* b, const float* gout, void* ga, void* gb, int64_t n, int a_dtype, int b_dtype,
                        const int64_t* shape4, const int64_t* a_strides4, const int64_t* b_strides4, void* stream);
 
+/* ---- linear-attention blocks of attn_layers (stylex_train.py:100-206), csrc/linattn.hip ------------------------------
+ * NHWC activations, fp32 (act_dtype 0) or bf16 (1); sums and exponentials in fp32; every reduction over pixels or
+ * batch is two-stage with the slices added in index order (no atomics).
+ *
+ * Attention core, 64 channels per head.  shape = {B, H*W, heads}.  q, k, v: channel stride 1, `strides` =
+ * {q_pixel, q_sample, k_pixel, k_sample, v_pixel, v_sample} in elements (multiples of 4; k and v may be the two
+ * channel halves of one tensor).  y, pre, gy, dq, dk, dv: dense [B][H*W][heads*64].
+ *   K = softmax over pixels of k,  Q = softmax over the 64 channels of q * 64^-0.5,  context = K^T v  [B][heads][64][64],
+ *   pre = Q context,  y = gelu_erf(pre),  lse = log-sum-exp of k over the pixels [B][heads][64].
+ * workspace (floats): fwd  B*heads*chunks*(64*64 + 128);  bwd  B*heads*(chunks + 1)*64*64 + B*heads*64,
+ * chunks = stylex_linattn_chunks(shape).  All pointers 16-byte aligned (8 for bf16 activations). */
+int stylex_linattn_chunks(const int64_t* shape);
+int stylex_linattn_fwd(const void* q, const void* k, const void* v, const int64_t* strides, void* y, void* pre, float* context,
+                       float* lse, float* workspace, const int64_t* shape, int act_dtype, void* stream);
+int stylex_linattn_bwd(const void* q, const void* k, const void* v, const int64_t* strides, const void* pre, const void* gy,
+                       const float* context, const float* lse, void* dq, void* dk, void* dv, float* workspace,
+                       const int64_t* shape, int act_dtype, void* stream);
+/* ChanNorm: y = (x - mean) / (sqrt(biased var) + eps) * g + b over the C channels of a pixel.  shape = {pixels, C},
+ * C = 4 << s, s in [0, 6] (else STYLEX_NOT_APPLICABLE).  mean, stdv: fp32 [pixels], written by fwd, read by bwd.
+ * bwd: gx may be NULL; partial = stylex_chan_norm_bwd_blocks(shape) * 2 * C floats and dgb = {dg[C], db[C]}, or both
+ * NULL when the parameter gradients are not wanted. */
+int stylex_chan_norm_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* stdv, const int64_t* shape,
+                         float eps, int act_dtype, void* stream);
+int stylex_chan_norm_bwd_blocks(const int64_t* shape);
+int stylex_chan_norm_bwd(const void* x, const void* gy, const float* g, const float* mean, const float* stdv, void* gx,
+                         float* partial, float* dgb, const int64_t* shape, float eps, int act_dtype, void* stream);
+/* Depthwise 3x3, pad 1, stride 1, no bias.  shape = {B, H, W, C}, C % 4 == 0; w fp32 [C][9].  The data gradient is
+ * the same call on gy with the nine taps mirrored.  Weight gradient: C = 4 << s, s in [0, 6]; partial =
+ * stylex_dwconv3x3_wgrad_blocks(shape) * C * 9 floats; dw fp32 [C][9]. */
+int stylex_dwconv3x3_fwd(const void* x, const float* w, void* y, const int64_t* shape, int act_dtype, void* stream);
+int stylex_dwconv3x3_wgrad_blocks(const int64_t* shape);
+int stylex_dwconv3x3_bwd_weight(const void* x, const void* gy, float* partial, float* dw, const int64_t* shape, int act_dtype,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
