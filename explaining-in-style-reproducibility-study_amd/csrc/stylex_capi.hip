@@ -36,10 +36,11 @@ std::mutex g_mu;
 bool g_timing = false;
 thread_local int t_timing_paused = 0;  // stylex_timing_pause: launches of the calling thread are not recorded (the frozen networks)
 std::vector<TimedLaunch> g_pending;
-int64_t g_launches[3] = {0, 0, 0};
-double g_ms[3] = {0, 0, 0};
-double g_flops[3] = {0, 0, 0};
-double g_bytes[3] = {0, 0, 0};
+constexpr int NCLS = 4;  // conv fwd, bwd_data, bwd_weight, STYLEX_TIMING_INPUT
+int64_t g_launches[NCLS] = {0, 0, 0, 0};
+double g_ms[NCLS] = {0, 0, 0, 0};
+double g_flops[NCLS] = {0, 0, 0, 0};
+double g_bytes[NCLS] = {0, 0, 0, 0};
 
 struct ScopedTimer {
     bool on;
@@ -138,6 +139,9 @@ void stylex_note_kernel(const char* fmt, ...) {
     va_end(ap);
 }
 
+StylexTimedCall::StylexTimedCall(int cls, double bytes, hipStream_t s) : impl_(new ScopedTimer(cls, 0.0, bytes, s)) {}
+StylexTimedCall::~StylexTimedCall() { delete static_cast<ScopedTimer*>(impl_); }
+
 extern "C" {
 
 const char* stylex_version(void) { return "stylex-hip 0.1 (gfx950)"; }
@@ -158,7 +162,7 @@ int stylex_timing_enable(int on) {
     std::lock_guard<std::mutex> lk(g_mu);
     g_timing = on != 0;
     if (on) {
-        for (int i = 0; i < 3; ++i) {
+        for (int i = 0; i < NCLS; ++i) {
             g_launches[i] = 0;
             g_ms[i] = 0;
             g_flops[i] = 0;
@@ -211,7 +215,7 @@ int stylex_timing_layers(int64_t* meta, double* vals, int64_t cap) {
 }
 
 int stylex_timing_report(int cls, int64_t* launches, double* total_ms, double* total_flops, double* total_bytes) {
-    if (cls < 0 || cls > 2) return STYLEX_EINVAL;
+    if (cls < 0 || cls >= NCLS) return STYLEX_EINVAL;
     drain_pending();
     std::lock_guard<std::mutex> lk(g_mu);
     if (launches) *launches = g_launches[cls];

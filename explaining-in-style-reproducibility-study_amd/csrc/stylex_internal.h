@@ -65,6 +65,19 @@ int stylex_launch_pack(const float* w, void* wf, void* wb, int N, int C, int T, 
 // (printf-style; thread-local, no allocation).  A timed C-ABI call attributes its hipEvent interval to the LAST name
 // noted inside it (the main kernel of a multi-launch call notes itself last).
 void stylex_note_kernel(const char* fmt, ...);
+// The same hook for C-ABI calls that live outside stylex_capi.hip: the launches between construction and destruction are
+// one timed call of class `cls` (hipEvents on `s`; nothing happens while the hook is off or paused on this thread).
+#define STYLEX_TIMING_INPUT 3  // kernel class of the device input pipeline (resample_u8.hip), next to 0/1/2 = the convs
+class StylexTimedCall {
+  public:
+    StylexTimedCall(int cls, double bytes, hipStream_t s);
+    ~StylexTimedCall();
+    StylexTimedCall(const StylexTimedCall&) = delete;
+    StylexTimedCall& operator=(const StylexTimedCall&) = delete;
+
+  private:
+    void* impl_;
+};
 
 #ifdef __HIPCC__
 // bit k = (bf16 element k of the 16-byte vector > 0), with the float comparison the tensor-gate path uses

@@ -167,6 +167,13 @@ SIGNATURES = {
     "stylex_dwconv3x3_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_void_p]),
     "stylex_dwconv3x3_wgrad_blocks": (ctypes.c_int, [_i64p]),
     "stylex_dwconv3x3_bwd_weight": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_resample_rows_u8": (ctypes.c_int, [ctypes.c_void_p, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_f,
+                                               ctypes.c_int64, _c_f, ctypes.c_int64, ctypes.c_void_p]),
+    "stylex_resample_cols_u8": (ctypes.c_int, [ctypes.c_void_p, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_f,
+                                               ctypes.c_int64, _c_f, ctypes.c_int64, _c_f, _c_f, ctypes.c_int64,
+                                               ctypes.c_void_p]),
+    "stylex_crop_lut_u8": (ctypes.c_int, [ctypes.c_void_p, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_f,
+                                          ctypes.c_int64, _c_f, _c_f, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_timing_report": (ctypes.c_int, [ctypes.c_int, _i64p, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }
@@ -1776,7 +1783,7 @@ def timing_kernels(cap=256):
     meta = (ctypes.c_int64 * (cap * 2))()
     vals = (ctypes.c_double * (cap * 3))()
     n = lib.stylex_timing_kernels(names, meta, vals, cap)
-    cls = ("fwd", "bwd_data", "bwd_weight")
+    cls = ("fwd", "bwd_data", "bwd_weight", "input")
     rows = [dict(cls=cls[meta[r * 2]], kernel=names.raw[r * 112:(r + 1) * 112].split(b"\0", 1)[0].decode(),
                  launches=meta[r * 2 + 1], ms=vals[r * 3], flops=vals[r * 3 + 1], bytes=vals[r * 3 + 2]) for r in range(n)]
     KERNELS_SEEN.update((r["cls"], r["kernel"]) for r in rows if r["kernel"])
@@ -1918,3 +1925,40 @@ def linattn_bwd(q, k, v, pre, context, lse, gy, heads):
     _check(lib.stylex_linattn_bwd(_ptr(q), _ptr(k), _ptr(v), strides, _ptr(pre), _ptr(gy), _ptr(context), _ptr(lse), _ptr(dq),
                                   _ptr(dk), _ptr(dv), _ptr(ws), sh, _adt(q), _stream()), "stylex_linattn_bwd")
     return dq, dk, dv
+
+
+# ---- device input pipeline (csrc/resample_u8.hip) ---------------------------------------------------------------------
+
+def resample_supported(c, staging_bytes, out_floats, inter_pixels):
+    """The ragged-batch kernels take 3 or 4 channels and address every buffer with int32 offsets."""
+    return c in (3, 4) and 0 < staging_bytes < 2 ** 31 and 0 < out_floats < 2 ** 31 and 4 * inter_pixels < 2 ** 31
+
+
+def resample_batch(plan, host, dev, lut):
+    """Run an input_pipeline.BatchPlan: `host` / `dev` are the staging buffer (images, then the int32 job and coefficient
+    table) in pinned host memory and its uploaded copy; returns fp32 [B, C, s, s] = lut[byte] of the reference Dataset's
+    bytes.  At most five launches whatever the batch size: row and column pass of the resizes that read the uploaded
+    images, row and column pass of the second resize of augmented items, crop of the images that need no resize."""
+    lib = _ensure_device(dev)
+    assert dev.dtype == torch.uint8 and dev.numel() == plan.total_bytes and lut.dtype == torch.float32 and lut.numel() == 256
+    s, n, c = plan.s, plan.n, plan.c
+    out = _empty((n, c, s, s), dtype=torch.float32, device=dev.device)
+    inter = _empty(max(plan.inter_px, 1) * 4, dtype=torch.uint8, device=dev.device)
+    stage1 = _empty(max(plan.stage1_px, 1) * 4, dtype=torch.uint8, device=dev.device)
+    ints = plan.table.size
+    t_host = ctypes.c_void_p(host.data_ptr() + plan.image_bytes)
+    t_dev = ctypes.c_void_p(dev.data_ptr() + plan.image_bytes)
+    fj = [int(v) for v in plan.first_job]
+    nj = [len(lst) for lst in plan.lists]
+    stream = _stream()
+    for k, (src, src_bytes) in enumerate(((dev, plan.image_bytes), (stage1, plan.stage1_px * 4))):
+        if nj[2 * k]:
+            _check(lib.stylex_resample_rows_u8(t_host, t_dev, ints, fj[2 * k], nj[2 * k], _ptr(src), src_bytes, _ptr(inter),
+                                               plan.inter_px, stream), "stylex_resample_rows_u8")
+            _check(lib.stylex_resample_cols_u8(t_host, t_dev, ints, fj[2 * k + 1], nj[2 * k + 1], _ptr(inter), plan.inter_px * 4,
+                                               _ptr(stage1) if plan.stage1_px and k == 0 else None, plan.stage1_px, _ptr(lut),
+                                               _ptr(out), out.numel(), stream), "stylex_resample_cols_u8")
+    if nj[4]:
+        _check(lib.stylex_crop_lut_u8(t_host, t_dev, ints, fj[4], nj[4], _ptr(dev), plan.image_bytes, _ptr(lut), _ptr(out),
+                                      out.numel(), stream), "stylex_crop_lut_u8")
+    return out

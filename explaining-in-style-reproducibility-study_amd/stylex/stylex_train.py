@@ -22,6 +22,7 @@ import json
 import math
 import multiprocessing
 import os
+import random as pyrandom
 from math import floor, log2
 from pathlib import Path
 from random import random
@@ -406,21 +407,21 @@ def center_crop_offsets(w, h, s):
     return int(round((w - s) / 2.0)), int(round((h - s) / 2.0))
 
 
-def random_resized_crop_box(w, h, scale=(0.5, 1.0), ratio=(0.98, 1.02)):
+def random_resized_crop_box(w, h, scale=(0.5, 1.0), ratio=(0.98, 1.02), generator=None):
     """(top, left, height, width) of ``transforms.RandomResizedCrop.get_params`` (torchvision 0.11.1) with the
     reference's arguments (:537): up to 10 attempts, each drawing an area fraction and a log-uniform aspect ratio from
     torch's GLOBAL generator (``torch.empty(1).uniform_``), the first box that fits gets ``torch.randint`` offsets;
-    otherwise the central fallback box."""
+    otherwise the central fallback box.  `generator`: a torch.Generator to draw from instead (same draws, same order)."""
     area = h * w
     log_ratio = torch.log(torch.tensor(ratio))
     for _ in range(10):
-        target_area = area * torch.empty(1).uniform_(scale[0], scale[1]).item()
-        aspect = torch.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1])).item()
+        target_area = area * torch.empty(1).uniform_(scale[0], scale[1], generator=generator).item()
+        aspect = torch.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1], generator=generator)).item()
         cw = int(round(math.sqrt(target_area * aspect)))
         ch = int(round(math.sqrt(target_area / aspect)))
         if 0 < cw <= w and 0 < ch <= h:
-            top = torch.randint(0, h - ch + 1, size=(1,)).item()
-            left = torch.randint(0, w - cw + 1, size=(1,)).item()
+            top = torch.randint(0, h - ch + 1, size=(1,), generator=generator).item()
+            left = torch.randint(0, w - cw + 1, size=(1,), generator=generator).item()
             return top, left, ch, cw
     in_ratio = float(w) / float(h)
     if in_ratio < min(ratio):
@@ -812,15 +813,20 @@ class Trainer:
         if self.device_pipeline:
             import input_pipeline
 
-            # the decode-only dataset has no augmentation stage (the reference's RandomApply(aug_prob, crop + flip) runs
-            # on PIL images in the worker): refuse instead of silently training without it
-            assert not self.dataset_aug_prob, "device_pipeline=True does not implement dataset_aug_prob > 0"
-            ds = input_pipeline.RawImageFolder(folder, self.image_size, transparent=self.transparent)
+            # dataset_aug_prob: the decode-only dataset draws each item's RandomApply decision and crop box, the device
+            # crops and resizes.  Its in-process loader runs on the prefetch thread: draws from the global generators
+            # there would interleave with this thread's latent / noise draws differently from run to run, so the loader
+            # owns a private pair, seeded once from torch's global generator (workers are reseeded from it by the loader)
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+            py_rng, torch_rng = pyrandom.Random(seed), torch.Generator().manual_seed(seed)
+            ds = input_pipeline.RawImageFolder(folder, self.image_size, transparent=self.transparent,
+                                               aug_prob=self.dataset_aug_prob, py_rng=py_rng, torch_rng=torch_rng)
             sampler = DistributedSampler(ds, rank=self.rank, num_replicas=self.world_size,
                                          shuffle=True) if self.is_ddp else None
             self.loader, self.dataset = input_pipeline.make_device_loader(
                 ds, self.image_size, math.ceil(self.batch_size / self.world_size), self.device,
-                num_workers=num_workers, transparent=self.transparent, sampler=sampler, shuffle=not self.is_ddp)
+                num_workers=num_workers, transparent=self.transparent, sampler=sampler, shuffle=not self.is_ddp,
+                generator=torch_rng)
         else:
             self.dataset = Dataset(folder, self.image_size, transparent=self.transparent, aug_prob=self.dataset_aug_prob)
             sampler = DistributedSampler(self.dataset, rank=self.rank, num_replicas=self.world_size,

@@ -411,7 +411,8 @@ int stylex_torgb_bwd(const void* x, const void* gy, const float* s1, const float
 /* Per-kernel timing hook: when enabled every conv launch is bracketed
  * by hipEvents on its stream; stylex_timing_report returns, per kernel class
  * (0=fwd,1=bwd_data,2=bwd_weight): launches, total ms, total algorithmic FLOPs and total algorithmic HBM
- * bytes (activations in + out once at their storage width, weights once). */
+ * bytes (activations in + out once at their storage width, weights once).  Class 3 = the launches of the device input
+ * pipeline (stylex_resample_*_u8, stylex_crop_lut_u8; no FLOPs). */
 int stylex_timing_enable(int on);
 /* on != 0: the CALLING THREAD's launches are not recorded until the matching stylex_timing_pause(0) (nestable) — the frozen
  * networks' layers that run on these kernels (bf16 LPIPS-AlexNet, the classifier's data gradient) stay out of the StylEx
@@ -523,6 +524,37 @@ int stylex_dwconv3x3_fwd(const void* x, const float* w, void* y, const int64_t* 
 int stylex_dwconv3x3_wgrad_blocks(const int64_t* shape);
 int stylex_dwconv3x3_bwd_weight(const void* x, const void* gy, float* partial, float* dw, const int64_t* shape, int act_dtype,
                                 void* stream);
+
+
+/* ---- device input pipeline (stylex/input_pipeline.py), csrc/resample_u8.hip ------------------------------------------
+ * PIL's 8-bit Image.resize(size, BILINEAR) in integers — a horizontal and a vertical pass with 22-bit fixed-point
+ * coefficients, each rounding to bytes: out = clip(((1 << 21) + sum_t in[first + t] * k[t]) >> 22, 0, 255) — plus the RGBA
+ * premultiplied round trip, crop, and the final planar fp32 store lut[byte].  Bit-identical to PIL; no float arithmetic on
+ * pixel values, no atomics.
+ *
+ * One launch serves a ragged batch: `table` is an int32 array holding jobs of 20 ints each (job n at table[20 * n]) and,
+ * behind them, the per-axis tables the jobs point to.  The caller passes the table twice: its host copy (checked here,
+ * before anything is launched) and its device copy (read by the kernel).  Job fields, in order:
+ *   src_off (bytes, in `src`), src_h, src_w, src_bpp (3 or 4 bytes per source pixel), C (3 or 4 channels, <= src_bpp),
+ *   in0 (source index that tap index 0 refers to: origin of the resized box along the pass axis),
+ *   o0, o1 (output index range along the pass axis), p0, p1 (source index range along the other axis),
+ *   bounds_off (table offset of {first tap, tap count} per output index), coef_off (ksize coefficients per output index),
+ *   ksize, dst_off, dst_stride, dst_plane (destination elements), flags, 3 reserved ints.
+ * flags: 1 premultiply colours by alpha on load (rows, C = 4), 2 divide them out on store (cols, C = 4), 4 store
+ * lut[byte] as fp32 at out[dst_off + c * dst_plane + row * dst_stride + col] instead of a 4-byte pixel at
+ * dst[dst_off + row * dst_stride + col].
+ *   rows: src = uint8 [src_h][src_w][src_bpp]; for source rows [p0, p1) and output columns [o0, o1) -> 4-byte pixels.
+ *   cols: src = 4-byte pixels [src_h][src_w]; for output rows [o0, o1) and columns [p0, p1) -> 4-byte pixels or lut store.
+ *   crop: rows [o0, o1), columns [p0, p1) of src -> lut store (flag 4 required).
+ * STYLEX_EINVAL, before the device is touched: a null pointer, C or src_bpp outside {3, 4}, an empty window, a window or a
+ * tap range outside its image, an image outside `src`, a store outside its destination, more than 65535 jobs. */
+int stylex_resample_rows_u8(const int32_t* table_host, const int32_t* table_dev, int64_t table_ints, int64_t first_job,
+                            int64_t njobs, const void* src, int64_t src_bytes, void* dst, int64_t dst_pixels, void* stream);
+int stylex_resample_cols_u8(const int32_t* table_host, const int32_t* table_dev, int64_t table_ints, int64_t first_job,
+                            int64_t njobs, const void* src, int64_t src_bytes, void* dst, int64_t dst_pixels, const float* lut,
+                            float* out, int64_t out_floats, void* stream);
+int stylex_crop_lut_u8(const int32_t* table_host, const int32_t* table_dev, int64_t table_ints, int64_t first_job, int64_t njobs,
+                       const void* src, int64_t src_bytes, const float* lut, float* out, int64_t out_floats, void* stream);
 
 #ifdef __cplusplus
 }
