@@ -24,6 +24,9 @@ import weakref
 
 import torch
 
+import operand_cache
+from operand_cache import mark_updated, packs, stamp as _gen, vectors  # noqa: F401  (re-exported: ops, the Trainer, tests)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libstylex_hip.so")
 
@@ -261,6 +264,9 @@ def _stream_id():
     return int(torch.cuda.current_stream().cuda_stream)
 
 
+operand_cache.stream_id = _stream_id
+
+
 def _ensure_device(t):
     if not t.is_cuda:
         raise StylexHipError("stylex HIP ops need a GPU tensor (got %s); the product path has no CPU fallback"
@@ -377,23 +383,9 @@ def empty_cl(shape, like, dtype=None):
     return _empty(shape, dtype=dtype or like.dtype, device=like.device, memory_format=torch.channels_last)
 
 
-_PACK_CACHE = {}
-_PACK_CACHE_MAX = 512
-# STYLEX_CACHE_CHECK=1 (debug; costs a host sync per lookup): every cache entry remembers a checksum of the parameter
-# it was packed from, and a hit whose parameter no longer has that checksum raises — the failure mode of round 3's
-# stale-operand bug (an update path that bumps neither Parameter._version nor the `mark_updated` stamp).
-_CACHE_CHECK = os.environ.get("STYLEX_CACHE_CHECK", "0") == "1"
-
-
-def _checksum(w):
-    w = w.detach().double()
-    return (float(w.sum()), float(w.abs().sum()))
-
-
-
 def pack_cache_clear():
-    _PACK_CACHE.clear()
-    _PARAM_KEYS.clear()
+    packs.clear()
+    vectors.clear()
 
 
 def _release_at_exit():
@@ -404,69 +396,10 @@ def _release_at_exit():
             torch.cuda.synchronize()
     except Exception:  # noqa: BLE001
         pass
-    _PACK_CACHE.clear()
+    pack_cache_clear()
 
 
 atexit.register(_release_at_exit)
-
-
-_CACHE_ON = os.environ.get("STYLEX_PACK_CACHE", "1") != "0"  # probe switch: 0 = repack on every use
-
-
-def _gen(t):
-    """Modification stamp of a parameter: torch's version counter AND our own generation counter.  The fused Adam
-    (torch._fused_adam_, the speed mode's optimiser) updates parameters WITHOUT bumping `_version` (measured: 0 -> 0
-    across a step, foreach / plain Adam 0 -> 1), so the Trainer stamps every parameter it steps (`mark_updated`)."""
-    return None if t is None else (t._version, getattr(t, "_stylex_gen", 0))
-
-
-def mark_updated(params):
-    """Call after an optimiser step that may not bump Parameter._version: invalidates the cached operand copies."""
-    for p in params:
-        p._stylex_gen = getattr(p, "_stylex_gen", 0) + 1
-
-
-def _cache_hit(key, w, version=None):
-    """One entry per (parameter, operand variant): valid while the parameter's version counter (bumped by every
-    in-place update, i.e. by the optimiser step) is the one it was packed from.  Cached packs may have been produced
-    on another HIP stream (the Trainer forks independent branches over side streams, `prepack` runs on its own): make
-    the consumer stream wait for the producing kernel and keep the block alive for it."""
-    hit = _PACK_CACHE.get(key) if _CACHE_ON else None
-    if hit is None or hit[0]() is not w:  # same live Parameter object (its address cannot be recycled)
-        return None
-    if hit[5] != (_gen(w) if version is None else version):
-        return None
-    if _CACHE_CHECK and hit[6] is not None:  # debug: a hit whose source changed without a stamp is a stale operand
-        now = _checksum(w)
-        if now != hit[6]:
-            raise RuntimeError("stale operand pack served for %r: the parameter changed (checksum %r -> %r) without "
-                               "Parameter._version / hb.mark_updated() advancing" % (key, hit[6], now))
-    if hit[4] != _stream_id():  # raw handles first: building a Stream object costs more than the whole lookup
-        cur = torch.cuda.current_stream()
-        cur.wait_event(hit[3])
-        for t in (hit[1], hit[2]):
-            if t is not None:
-                t.record_stream(cur)
-    return hit[1], hit[2]
-
-
-_PACK_RECIPES = {}  # key -> (weakref to the parameter, function that packs it again): what `prepack` replays
-_PARAM_KEYS = {}    # id(parameter) -> keys of its cache entries (adam_pack_step rewrites them in place)
-
-
-def _cache_put(key, w_param, wf, wb, version=None, recipe=None):
-    if len(_PACK_CACHE) >= _PACK_CACHE_MAX:
-        _PACK_CACHE.clear()
-        _PARAM_KEYS.clear()
-    ev = torch.cuda.Event()
-    ev.record()
-    _PACK_CACHE[key] = (weakref.ref(w_param), wf, wb, ev, _stream_id(),
-                        _gen(w_param) if version is None else version, _checksum(w_param) if _CACHE_CHECK else None)
-    _PARAM_KEYS.setdefault(id(w_param), set()).add(key)
-    if recipe is not None:
-        if len(_PACK_RECIPES) >= 4 * _PACK_CACHE_MAX:
-            _PACK_RECIPES.clear()
-        _PACK_RECIPES[key] = (weakref.ref(w_param), recipe)
 
 
 _PREPACK_STREAMS = {}
@@ -476,28 +409,20 @@ def prepack(params):
     """Re-pack, on a side stream, every cached operand variant of `params` whose parameter has changed — called right
     after an optimiser step, so that the ~20 tiny pack launches per network run under the following kernels instead of
     in front of each layer's first use (they sat on the critical chain: 66 launches, 1.4 ms of kernel time per step).
-    Consumers synchronise through the cache entry's event (`_cache_hit`)."""
-    if not _CACHE_ON or not _PACK_RECIPES:
+    Consumers synchronise through the cache entry's event (`operand_cache.Cache.lookup`)."""
+    if not operand_cache.ON or not packs.recipes:
         return
-    ids = {id(p) for p in params}
-    todo = []
-    for key, (ref, fn) in list(_PACK_RECIPES.items()):
-        w = ref()
-        if w is None:
-            del _PACK_RECIPES[key]
-            _PACK_CACHE.pop(key, None)
-        elif id(w) in ids and w.is_cuda:
-            todo.append((w, fn))
+    todo = [(owners, fn) for owners, fn in packs.replay(params) if owners[0].is_cuda]
     if not todo:
         return
-    dev = todo[0][0].device
+    dev = todo[0][0][0].device  # (first owner of the first entry)
     side = _PREPACK_STREAMS.get(dev)
     if side is None:
         side = _PREPACK_STREAMS[dev] = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))  # the optimiser's writes
     with torch.cuda.stream(side):
-        for w, fn in todo:
-            fn(w)
+        for owners, fn in todo:
+            fn(*owners)
 
 
 # ---- Adam step + refresh of the cached operand copies in ONE launch (csrc/adam_pack.hip) --------------------------------
@@ -520,30 +445,24 @@ def _adam_dtype():
     return _ADAM_DT
 
 
+_ADAM_KIND_CODE = {"pack": 0, "s2d": 1, "bf16mat": 0, "wsq": 2}  # stylex_adam_tensor.var[].kind; other kinds stay lazy
+
+
 def _adam_copies_of(p):
-    """Cache entries (key, kind, scale, a, b) of parameter `p` that the fused step can rewrite from the updated value:
-    bf16 operand packs (plain and space-to-depth), the bf16 GEMM matrix of a 1x1 weight, the tap sum of squares.  Other
-    derived copies (mirrored-tap packs of the penalty pass, fp32 packs, scaled linear parameters) stay lazy."""
+    """Cache entries (entry, kind code, scale, a, b) of parameter `p` that the fused step can rewrite from the updated
+    value: bf16 operand packs (plain and space-to-depth), the bf16 GEMM matrix of a 1x1 weight ([N][C*T] == the forward
+    pack of a T = 1 conv), the tap sum of squares.  Other copies (packs of a padded copy, mirrored-tap packs of the
+    penalty pass, fp32 packs, scaled linear parameters) stay lazy.  In descriptor slot order."""
     out = []
-    ptr, shape = p.data_ptr(), tuple(p.shape)
-    for key in _PARAM_KEYS.get(id(p), ()):
-        hit = _PACK_CACHE.get(key)
-        if hit is None or hit[0]() is not p or len(key) != 4 or key[0] != ptr or key[1] != shape:
+    for e in packs.entries_of(p):
+        code = _ADAM_KIND_CODE.get(e.kind)
+        if code is None or e.derived or (e.kind == "pack" and e.precision == F32):
             continue
-        tag, scale = key[2], key[3]
-        if isinstance(scale, str):  # mirrored-tap packs of the penalty pass ("fwd_as_dgrad"): stay lazy
-            continue
-        a, b = hit[1], hit[2]
-        sc = 1.0 if scale is None else float(scale)
-        if tag in (BF16, BF16_ACT) and len(shape) == 4 and all(t is None or t.dtype == torch.bfloat16 for t in (a, b)):
-            out.append((key, 0, sc, a, b))
-        elif tag == "s2d" and len(shape) == 4 and shape[2] == 3 and shape[3] == 3:
-            out.append((key, 1, sc, a, b))
-        elif tag == "bf16mat" and a is not None and a.dtype == torch.bfloat16:
-            out.append((key, 0, sc, a, None))  # [N][C*T] matrix == the forward pack of a T = 1 conv
-        elif tag == "wsq" and a is not None and a.dtype == torch.float32:
-            out.append((key, 2, 1.0, a, None))
-    return out
+        a, b = (e.value + (None,))[:2]
+        want = torch.float32 if e.kind == "wsq" else torch.bfloat16  # what the kernel writes through the raw pointers
+        if all(t is None or t.dtype == want for t in (a, b)):
+            out.append((str(e.precision) if e.kind == "pack" else e.kind, 1.0 if e.scale is None else float(e.scale), code, e, a, b))
+    return [(e, code, sc, a, b) for _, sc, code, e, a, b in sorted(out, key=lambda c: c[:3])]
 
 
 _ADAM_COPY_OVERFLOW = False
@@ -590,14 +509,14 @@ def adam_pack_step(opt):
     dev = todo[0][0].device
     dt = _adam_dtype()
     # ---- plan: everything but the gradient pointers is stable from step to step
-    copies_of = {id(p): sorted(_adam_copies_of(p), key=lambda e: (str(e[0][2]), e[2], e[1])) for p, _, _ in todo}
+    copies_of = {id(p): _adam_copies_of(p) for p, _, _ in todo}
     # the signature covers everything the device descriptors hold a raw pointer / constant of: the parameter, its
     # moment and step tensors (load_state_dict installs NEW ones while the parameter keeps its address), the
     # hyper-parameters baked into the descriptor, and the registered copies
     sig = tuple((id(p), p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr(),
                  float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                 tuple((str(k[2]), sc, 0 if a is None else a.data_ptr(), 0 if b is None else b.data_ptr())
-                       for k, _, sc, a, b in copies_of[id(p)]))
+                 tuple((id(e), sc, 0 if a is None else a.data_ptr(), 0 if b is None else b.data_ptr())
+                       for e, _, sc, a, b in copies_of[id(p)]))
                 for p, st, g in todo)
     plan = _ADAM_PLANS.get(id(opt))
     if plan is None or plan["sig"] != sig or plan["opt_ref"]() is not opt:  # (a recycled id(opt) must not inherit a plan)
@@ -631,11 +550,11 @@ def adam_pack_step(opt):
             r["p"], r["m"], r["v"], r["step"] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr()
             r["numel"], r["N"], r["C"], r["T"], r["nvar"], r["first_block"] = p.numel(), n, c, t, len(copies), nb
             r["lr"], r["beta1"], r["beta2"], r["eps"] = g["lr"], g["betas"][0], g["betas"][1], g["eps"]
-            for j, (key, kind, sc, a, b) in enumerate(copies):
+            for j, (e, kind, sc, a, b) in enumerate(copies):
                 r["var"][j]["kind"], r["var"][j]["scale"] = kind, sc
                 r["var"][j]["a"] = 0 if a is None else a.data_ptr()
                 r["var"][j]["b"] = 0 if b is None else b.data_ptr()
-                entries.append((key, p))
+                entries.append(e)
             block_map.append(np.full(blocks, i, dtype=np.int32))
             nb += blocks
         bm = torch.from_numpy(np.concatenate(block_map)).to(dev)
@@ -663,10 +582,8 @@ def adam_pack_step(opt):
         ev = torch.cuda.Event()
         ev.record()
         sid = _stream_id()
-        for key, p in plan["entries"]:
-            hit = _PACK_CACHE.get(key)
-            if hit is not None and hit[0]() is p:
-                _PACK_CACHE[key] = (hit[0], hit[1], hit[2], ev, sid, _gen(p), _checksum(p) if _CACHE_CHECK else None)
+        for e in plan["entries"]:
+            packs.revalidate(e, ev, sid)
     return True
 
 
@@ -676,41 +593,26 @@ def prepack_join():
         torch.cuda.current_stream(dev).wait_stream(side)
 
 
+def _packable(w):
+    """The pack kernels' source format: what a cached operand copy is made from without a conversion."""
+    return w.is_contiguous() and w.dtype == torch.float32
+
+
 def scaled_linear_params(w, b, lr_mul):
     """(w * lr_mul, b * lr_mul) of an equalised-learning-rate linear layer (EqualLinear.forward, reference
     :585-586), cached until the optimiser modifies the parameters: the mapping network runs 2-4 times per step on the
     same weights, and each run used to issue the two multiplies again (8 layers x 2 launches per run)."""
     _ensure_device(w)
-    key = ("eql", w.data_ptr(), None if b is None else b.data_ptr(), tuple(w.shape), float(lr_mul))
-    cacheable = isinstance(w, torch.nn.Parameter)
-    ver = (_gen(w), _gen(b))
-    hit = _cache_hit(key, w, ver) if cacheable else None
-    if hit is not None:
-        return hit
-    with torch.no_grad():
-        ws = w.detach() * lr_mul
-        bs = None if b is None else b.detach() * lr_mul
-    if cacheable:
-        bref = None if b is None else weakref.ref(b)
-        _cache_put(key, w, ws, bs, ver, recipe=lambda p: scaled_linear_params(p, None if bref is None else bref(), lr_mul))
-    return ws, bs
+    return packs.get((w, b), "eql", lambda: (w.detach() * lr_mul, None if b is None else b.detach() * lr_mul),
+                     lr_mul=float(lr_mul), recipe=lambda w_, b_=None: scaled_linear_params(w_, b_, lr_mul))
 
 
 def pad_in_channels(w, extra):
     """OIHW parameter with `extra` zero input channels appended (the first conv of D / the encoder reads the RGB image
     padded to one 16-byte channel slot), cached per Parameter version: the block used to rebuild it with two launches
     (zeros + cat) in every forward and every backward."""
-    cacheable = isinstance(w, torch.nn.Parameter) and w.is_contiguous() and w.dtype == torch.float32 and w.is_cuda
-    key = None
-    if cacheable:
-        key = (w.data_ptr(), tuple(w.shape), "padc", int(extra))
-        hit = _cache_hit(key, w)
-        if hit is not None and hit[0] is not None:
-            return hit[0]
-    wp = torch.cat([w.detach(), w.new_zeros(w.shape[0], extra, w.shape[2], w.shape[3])], dim=1)
-    if key is not None:
-        _cache_put(key, w, wp, None)
-    return wp
+    return packs.get((w,), "padc", lambda: (torch.cat([w.detach(), w.new_zeros(w.shape[0], extra, w.shape[2], w.shape[3])], dim=1),),
+                     _packable(w) and w.is_cuda, extra=int(extra))[0]
 
 
 def pack_weight(w, want_fwd=True, want_bwd=False, precision=F32, scale=None, owner=None):
@@ -721,32 +623,31 @@ def pack_weight(w, want_fwd=True, want_bwd=False, precision=F32, scale=None, own
     tensor `w` was computed from (pad_in_channels): the pack is cached under the owner's modification stamp."""
     lib = _ensure_device(w)
     own = w if owner is None else owner
-    cacheable = isinstance(own, torch.nn.Parameter) and w.is_contiguous() and w.dtype == torch.float32
-    key = None
-    if cacheable:
-        key = (own.data_ptr(), tuple(w.shape), precision, scale) if owner is None else \
-            (own.data_ptr(), tuple(w.shape), precision, scale, "derived")
-        hit = _cache_hit(key, own)
-        if hit is not None and (hit[0] is not None or not want_fwd) and (hit[1] is not None or not want_bwd):
-            return hit
-        if scale is None:
-            want_fwd = want_bwd = True  # both operand layouts in one launch; a scaled pack is only ever used one way
-    w_param = own
-    w = w.contiguous()
-    if w.dtype != torch.float32:
-        w = w.float()
-    if scale is not None:
-        w = w.detach() * scale
-    n, c, kh, kw = w.shape
-    dt = torch.float32 if precision == F32 else torch.bfloat16
-    wf = _empty(n * kh * kw * c, dtype=dt, device=w.device) if want_fwd else None
-    wb = _empty(n * kh * kw * c, dtype=dt, device=w.device) if want_bwd else None
-    _check(lib.stylex_pack_weight(_ptr(w), _ptr(wf), _ptr(wb), _shape(n, c, kh, kw), precision, _stream()),
-           "stylex_pack_weight")
-    if key is not None:
-        _cache_put(key, w_param, wf, wb,
-                   recipe=(lambda p: pack_weight(p, want_fwd, want_bwd, precision, scale)) if owner is None else None)
-    return wf, wb
+    cacheable = isinstance(own, torch.nn.Parameter) and _packable(w)
+    # a cached unscaled pack gets both operand layouts in one launch; a scaled pack is only ever used one way
+    both = cacheable and scale is None
+    mk_fwd, mk_bwd = want_fwd or both, want_bwd or both
+
+    def build():
+        wc = w.contiguous().float()
+        if scale is not None:
+            wc = wc.detach() * scale
+        n, c, kh, kw = wc.shape
+        dt = torch.float32 if precision == F32 else torch.bfloat16
+        wf = _empty(n * kh * kw * c, dtype=dt, device=wc.device) if mk_fwd else None
+        wb = _empty(n * kh * kw * c, dtype=dt, device=wc.device) if mk_bwd else None
+        _check(lib.stylex_pack_weight(_ptr(wc), _ptr(wf), _ptr(wb), _shape(n, c, kh, kw), precision, _stream()),
+               "stylex_pack_weight")
+        return wf, wb
+
+    def usable(e):
+        wf, wb = e.value
+        return (wf is not None or not want_fwd) and (wb is not None or not want_bwd)
+
+    derived = owner is not None  # (no recipe then: it could only re-pack the owner itself)
+    return packs.get((own,), "pack", build, cacheable, usable, precision=precision, scale=scale, derived=derived,
+                     extra=w.shape[1] - own.shape[1] if derived else None,
+                     recipe=None if derived else lambda p: pack_weight(p, mk_fwd, mk_bwd, precision, scale))
 
 
 def pack_weight_fwd_as_dgrad(w, precision):
@@ -756,44 +657,35 @@ def pack_weight_fwd_as_dgrad(w, precision):
     weight is w transposed and tap-mirrored — so the operand is the forward layout [N][tap][C] of the tap-mirrored w.
     Cached per Parameter version like the other packs."""
     lib = _ensure_device(w)
-    cacheable = isinstance(w, torch.nn.Parameter) and w.is_contiguous() and w.dtype == torch.float32
-    key = None
-    if cacheable:
-        key = (w.data_ptr(), tuple(w.shape), precision, "fwd_as_dgrad")
-        hit = _cache_hit(key, w)
-        if hit is not None:
-            return hit[0]
-    wm = w.detach().float().flip(2, 3).contiguous()
-    n, c, kh, kw = wm.shape
-    dt = torch.float32 if precision == F32 else torch.bfloat16
-    wf = _empty(n * kh * kw * c, dtype=dt, device=w.device)
-    _check(lib.stylex_pack_weight(_ptr(wm), _ptr(wf), None, _shape(n, c, kh, kw), precision, _stream()), "stylex_pack_weight")
-    if key is not None:
-        _cache_put(key, w, wf, None, recipe=lambda p: pack_weight_fwd_as_dgrad(p, precision))
-    return wf
+
+    def build():
+        wm = w.detach().float().flip(2, 3).contiguous()
+        n, c, kh, kw = wm.shape
+        wf = _empty(n * kh * kw * c, dtype=torch.float32 if precision == F32 else torch.bfloat16, device=w.device)
+        _check(lib.stylex_pack_weight(_ptr(wm), _ptr(wf), None, _shape(n, c, kh, kw), precision, _stream()), "stylex_pack_weight")
+        return (wf,)
+
+    return packs.get((w,), "fwd_as_dgrad", build, _packable(w), precision=precision,
+                     recipe=lambda p: pack_weight_fwd_as_dgrad(p, precision))[0]
 
 
 def pack_weight_s2d(w, scale=None):
     """OIHW {N,C,3,3} parameter of a stride-2 conv -> bf16 operands of its space-to-depth form (cached)."""
     lib = _ensure_device(w)
-    key = None
-    if isinstance(w, torch.nn.Parameter) and w.is_contiguous() and w.dtype == torch.float32:
-        key = (w.data_ptr(), tuple(w.shape), "s2d", scale)
-        hit = _cache_hit(key, w)
-        if hit is not None:
-            return hit
-    wc = w.contiguous().float()
-    if scale is not None:
-        wc = wc.detach() * scale
-    n, c, kh, kw = wc.shape
-    assert kh == 3 and kw == 3
-    wf = _empty(n * 36 * c, dtype=torch.bfloat16, device=w.device)
-    wb = _empty(n * 36 * c, dtype=torch.bfloat16, device=w.device)
-    _check(lib.stylex_pack_weight_s2d(_ptr(wc), _ptr(wf), _ptr(wb), _shape(n, c, 3, 3), _stream()),
-           "stylex_pack_weight_s2d")
-    if key is not None:
-        _cache_put(key, w, wf, wb, recipe=lambda p: pack_weight_s2d(p, scale))
-    return wf, wb
+
+    def build():
+        wc = w.contiguous().float()
+        if scale is not None:
+            wc = wc.detach() * scale
+        n, c, kh, kw = wc.shape
+        assert kh == 3 and kw == 3
+        wf = _empty(n * 36 * c, dtype=torch.bfloat16, device=w.device)
+        wb = _empty(n * 36 * c, dtype=torch.bfloat16, device=w.device)
+        _check(lib.stylex_pack_weight_s2d(_ptr(wc), _ptr(wf), _ptr(wb), _shape(n, c, 3, 3), _stream()),
+               "stylex_pack_weight_s2d")
+        return wf, wb
+
+    return packs.get((w,), "s2d", build, _packable(w), scale=scale, recipe=lambda p: pack_weight_s2d(p, scale))
 
 
 _S2D_WGRAD_OK = {}
@@ -1201,47 +1093,20 @@ def lpips_tap_bwd(f0, f1, lin, r0, r1, gout, want0, want1):
 def _bf16_matrix(w, scale=None, owner=None):
     """[N, C] bf16 copy of a 1x1 conv weight (x scale), cached per Parameter version like the packed operands
     (`owner`: as in pack_weight)."""
-    own = w if owner is None else owner
-    cacheable = isinstance(own, torch.nn.Parameter) and w.is_contiguous() and w.dtype == torch.float32
-    key = None
-    if cacheable:
-        key = (own.data_ptr(), tuple(w.shape), "bf16mat", scale) if owner is None else \
-            (own.data_ptr(), tuple(w.shape), "bf16mat", scale, "derived")
-        hit = _cache_hit(key, own)
-        if hit is not None and hit[0] is not None:
-            return hit[0]
-    m = w.detach().reshape(w.shape[0], -1)
-    m = (m * scale if scale is not None else m).to(torch.bfloat16).contiguous()
-    if key is not None:
-        _cache_put(key, own, m, None, recipe=(lambda p: _bf16_matrix(p, scale)) if owner is None else None)
-    return m
+    def build():
+        m = w.detach().reshape(w.shape[0], -1)
+        return ((m * scale if scale is not None else m).to(torch.bfloat16).contiguous(),)
 
-
-_VEC_CACHE = {}
+    derived = owner is not None
+    return packs.get((owner if derived else w,), "bf16mat", build, _packable(w), scale=scale, derived=derived,
+                     extra=w.shape[1] - owner.shape[1] if derived else None,
+                     recipe=None if derived else lambda p: _bf16_matrix(p, scale))[0]
 
 
 def cached_vector(tag, fn, *params):
     """fn(*params) for small per-layer vectors derived from Parameters (a bias in bf16, the sum of two biases), recomputed only
     when a parameter's modification stamp changes (round 6: ~45 tiny launches per step were recomputing them per use)."""
-    key = (tag,) + tuple(id(p) for p in params)
-    stamp = tuple(_gen(p) for p in params)
-    hit = _VEC_CACHE.get(key)
-    if hit is not None and hit[0] == stamp and all(r() is p for r, p in zip(hit[1], params)):
-        if hit[3] is not None and hit[4] != _stream_id():  # produced on another HIP stream: its kernel must have finished
-            cur = torch.cuda.current_stream()
-            cur.wait_event(hit[3])
-            hit[2].record_stream(cur)  # (its memory must not be recycled under this stream's reader once the entry is replaced)
-        return hit[2]
-    if len(_VEC_CACHE) > 4096:
-        _VEC_CACHE.clear()
-    v = fn(*[p.detach() for p in params])
-    if all(isinstance(p, torch.nn.Parameter) for p in params) and not (v.is_cuda and torch.cuda.is_current_stream_capturing()):
-        ev = None
-        if v.is_cuda:
-            ev = torch.cuda.Event()
-            ev.record()
-        _VEC_CACHE[key] = (stamp, tuple(weakref.ref(p) for p in params), v, ev, _stream_id() if v.is_cuda else None)
-    return v
+    return vectors.get(params, "vec", lambda: (fn(*[p.detach() for p in params]),), tag=tag)[0]
 
 
 def conv1x1_gemm_fwd(x, w, bias, owner=None):
@@ -1271,22 +1136,15 @@ def weight_sumsq(w):
     """wsq[o][i] = sum over the taps of w[o][i][.]^2 (fp32) — the weight-only factor of the demodulation coefficient;
     cached per Parameter version like the packed operands."""
     lib = _ensure_device(w)
-    cacheable = isinstance(w, torch.nn.Parameter) and w.is_contiguous() and w.dtype == torch.float32
-    key = None
-    if cacheable:
-        key = (w.data_ptr(), tuple(w.shape), "wsq", None)
-        hit = _cache_hit(key, w)
-        if hit is not None and hit[0] is not None:
-            return hit[0]
-    w_param = w
-    w = w.detach().contiguous().float()
-    o, c = w.shape[0], w.shape[1]
-    k = w.numel() // (o * c)
-    wsq = _empty(o * c, dtype=torch.float32, device=w.device).view(o, c)
-    _check(lib.stylex_weight_sumsq(_ptr(w), _ptr(wsq), o, c, k, _stream()), "stylex_weight_sumsq")
-    if key is not None:
-        _cache_put(key, w_param, wsq, None, recipe=weight_sumsq)
-    return wsq
+
+    def build():
+        wc = w.detach().contiguous().float()
+        o, c = wc.shape[0], wc.shape[1]
+        wsq = _empty(o * c, dtype=torch.float32, device=wc.device).view(o, c)
+        _check(lib.stylex_weight_sumsq(_ptr(wc), _ptr(wsq), o, c, wc.numel() // (o * c), _stream()), "stylex_weight_sumsq")
+        return (wsq,)
+
+    return packs.get((w,), "wsq", build, _packable(w), recipe=weight_sumsq)[0]
 
 
 def modcoeff_fwd(style, wsq, eps):

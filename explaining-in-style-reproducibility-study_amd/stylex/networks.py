@@ -293,7 +293,7 @@ class GeneratorBlock(nn.Module):  # reference :670-718
         if styles is None:
             # the block's three affine style maps as one GEMM (ops._StyleAffines); the first two column blocks ARE the
             # block's style coordinates (reference :716: cat(style1, style2)), the third is handed to to_rgb
-            fused = ops.style_affines(istyle, self.to_style1, self.to_style2, self.to_rgb.to_style, self.__dict__.setdefault("_aff_cache", {}))
+            fused = ops.style_affines(istyle, self.to_style1, self.to_style2, self.to_rgb.to_style)
             if fused is not None:
                 style1, style2, self._rgb_style, coords = fused
             else:

@@ -1303,13 +1303,9 @@ class _StyleAffines(torch.autograd.Function):
     The parameters stay the reference's three modules (state dict, AttFind's in-place bias edits)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, w3, b3, cache):
-        stamp = tuple(hb._gen(t) for t in (w1, b1, w2, b2, w3, b3))
-        hit = cache.get("cat")
-        if hit is None or hit[0] != stamp or hit[1].device != x.device:
-            hit = (stamp, torch.cat((w1.detach(), w2.detach(), w3.detach()), dim=0), torch.cat((b1.detach(), b2.detach(), b3.detach())))
-            cache["cat"] = hit
-        wcat, bcat = hit[1], hit[2]
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3):
+        wcat, bcat = hb.vectors.get((w1, b1, w2, b2, w3, b3), "vec", lambda: (
+            torch.cat((w1.detach(), w2.detach(), w3.detach()), dim=0), torch.cat((b1.detach(), b2.detach(), b3.detach()))), tag="affines")
         y = torch.addmm(bcat, x, wcat.t())
         ctx.save_for_backward(x, wcat)
         n1, n2, n3 = ctx.sizes = (w1.shape[0], w2.shape[0], w3.shape[0])
@@ -1333,10 +1329,10 @@ class _StyleAffines(torch.autograd.Function):
             gws = (gy.t() @ x).split((n1, n2, n3), dim=0)  # row blocks of one matrix: contiguous tensors
             gbs = gy.sum(dim=0).split((n1, n2, n3))
         return (gx, gws[0] if need[1] else None, gbs[0] if need[2] else None, gws[1] if need[3] else None,
-                gbs[1] if need[4] else None, gws[2] if need[5] else None, gbs[2] if need[6] else None, None)
+                gbs[1] if need[4] else None, gws[2] if need[5] else None, gbs[2] if need[6] else None)
 
 
-def style_affines(istyle, lin1, lin2, lin3, cache):
+def style_affines(istyle, lin1, lin2, lin3):
     """(to_style1(w), to_style2(w), to_rgb.to_style(w), [style1 | style2]) as four views of one GEMM result (the fused node
     above), or None when the composable path must run (CPU double, double backward, non-fp32 / non-2D input)."""
     if not (_IMPL is HipOps and istyle.is_cuda and istyle.dim() == 2 and fast_enabled() and istyle.dtype == torch.float32
@@ -1345,7 +1341,7 @@ def style_affines(istyle, lin1, lin2, lin3, cache):
     for lin in (lin1, lin2, lin3):
         if lin.bias is None or lin.weight.dtype != torch.float32:
             return None
-    return _StyleAffines.apply(istyle, lin1.weight, lin1.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias, cache)
+    return _StyleAffines.apply(istyle, lin1.weight, lin1.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias)
 
 
 class _ModCoeffs(torch.autograd.Function):

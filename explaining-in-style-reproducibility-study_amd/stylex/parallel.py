@@ -28,15 +28,15 @@ def broadcast_parameters(module, src=0):
     """Make every rank start from rank-``src`` weights and buffers."""
     if not is_dist():
         return
-    import hip_backend as hb  # pure-Python stamp; the library itself is only loaded by the first kernel call
+    import operand_cache
 
     with torch.no_grad():
         ts = list(module.parameters()) + list(module.buffers())
         for t in ts:
             dist.broadcast(t.detach(), src=src)  # detach() shares the version counter (t.data has its own)
     # the broadcast writes through a detached alias: stamp the parameters so that no cached operand pack made from the
-    # pre-broadcast weights can be served (hip_backend._gen)
-    hb.mark_updated(ts)
+    # pre-broadcast weights can be served (operand_cache.stamp)
+    operand_cache.mark_updated(ts)
 
 
 def _backend_averages():

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 import hip_backend as hb  # noqa: E402
+import operand_cache  # noqa: E402
 import ops  # noqa: E402
 import stylex_oracle as so  # noqa: E402
 import stylex_train as st  # noqa: E402
@@ -1449,7 +1450,7 @@ def test_style_affines_fused_node_vs_three_linears():
         wa = w.clone().requires_grad_()
         prev = ops.set_fast(True)
         try:
-            y = ops.style_affines(wa, *lins, blk.__dict__.setdefault("_aff_cache", {}))
+            y = ops.style_affines(wa, *lins)
         finally:
             ops.set_fast(prev)
         assert y is not None and len(y) == 4 and torch.equal(y[3], torch.cat(y[:2], dim=1))
@@ -2012,18 +2013,18 @@ def test_operand_cache_follows_parameter_versions_and_prepack():
         return F.conv2d(x.float(), w.detach().to(torch.bfloat16).float(), padding=1)
 
     close(ref(), conv(), 2e-2, "first pack")
-    n0 = len(hb._PACK_CACHE)
+    n0 = len(hb.packs)
     close(ref(), conv(), 2e-2, "cache hit")
-    assert len(hb._PACK_CACHE) == n0
+    assert len(hb.packs) == n0
     with torch.no_grad():
         w.mul_(-0.5)  # version bump without prepack: the stale entry must not be served
     close(ref(), conv(), 2e-2, "after an in-place update")
-    assert len(hb._PACK_CACHE) == n0, "one entry per (parameter, variant): replaced, not accumulated"
+    assert len(hb.packs) == n0, "one entry per (parameter, variant): replaced, not accumulated"
     with torch.no_grad():
         w.add_(1.0)
     hb.prepack([w])
-    key = next(k for k, v in hb._PACK_CACHE.items() if v[0]() is w)
-    assert hb._PACK_CACHE[key][5] == hb._gen(w) and hb._PACK_CACHE[key][4] != torch.cuda.current_stream().cuda_stream, \
+    entries = hb.packs.entries_of(w)
+    assert entries and all(e.stamps == (hb._gen(w),) and e.stream_id != torch.cuda.current_stream().cuda_stream for e in entries), \
         "prepack must have rebuilt the operand on its side stream"
     close(ref(), conv(), 2e-2, "after prepack")
     hb.prepack_join()
@@ -2036,6 +2037,10 @@ def test_operand_cache_follows_parameter_versions_and_prepack():
         hb.mark_updated([w])
     assert hb._gen(w) != before
     close(ref(), conv(), 2e-2, "after a fused-Adam step + mark_updated")
+    w.data = w.data.clone()  # same object, same version, new storage (module.to(...), EMA): the address is part of the rule
+    with torch.no_grad():
+        w.data.mul_(-2.0)
+    close(ref(), conv(), 2e-2, "after w.data = other")
 
 
 def test_generator_phase_sees_the_updated_discriminator(tmp_path):
@@ -2047,8 +2052,8 @@ def test_generator_phase_sees_the_updated_discriminator(tmp_path):
     g = load_golden("steps_gae2_alt")
     rows = {}
     for cache_on in (True, False):
-        prev = hb._CACHE_ON
-        hb._CACHE_ON = cache_on
+        prev = operand_cache.ON
+        operand_cache.ON = cache_on
         hb.pack_cache_clear()
         try:
             ops.set_precision("bf16")
@@ -2056,7 +2061,7 @@ def test_generator_phase_sees_the_updated_discriminator(tmp_path):
             tr, n = make_trainer(g, tmp_path / ("c%d" % cache_on), device=torch.device(DEV))
             rows[cache_on] = run_steps(tr, 3)
         finally:
-            hb._CACHE_ON = prev
+            operand_cache.ON = prev
             ops.set_precision("fp32")
     np.testing.assert_allclose(rows[True], rows[False], rtol=1e-6, atol=1e-6, equal_nan=True)
 
@@ -2719,7 +2724,7 @@ def test_adam_pack_step_matches_torch_fused_adam_and_the_pack_kernels():
     for k in (1, 2, 3):
         grads(ref_p, k), grads(ps, k)
         ref_opt.step()
-        before = {key: (e[1], e[2]) for key, e in hb._PACK_CACHE.items()}
+        before = {id(e): e.value for p in ps + [frozen] for e in hb.packs.entries_of(p)}
         assert hb.adam_pack_step(opt) is True
         for a, b in zip(ps, ref_p):
             close(b, a, 2e-6, "parameter after step %d" % k)
