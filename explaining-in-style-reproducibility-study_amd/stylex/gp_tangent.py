@@ -19,13 +19,14 @@ that produced u) serve both terms:
 Passes over D for the real branch of a penalty step: primal forward, unit data-gradient chain, tangent forward, ONE
 weight-gradient pass — 4 instead of the 6 of the double backward (forward, data gradient, [forward + weight gradient]
 of the second differentiation, [data + weight gradient] of the primal graph), all on the fused first-order kernels of
-ops._DBlockFast (gate epilogues, bit masks) instead of the composable double-differentiable ops.
+the fused DiscriminatorBlock (gate epilogues, bit masks) instead of the composable double-differentiable ops.  The primal
+forward and the unit chain ARE ops._dblock_forward / ops._dblock_backward, the stage functions behind ops._DBlockFast;
+the tangent forward follows each block's plan and named saved state and shares the block's helpers.
 
 Used by Trainer._d_compute for the default architecture in the bf16 speed mode (STYLEX_GP_TANGENT=0 restores the double
 backward; the fp32 parity mode keeps the reference's formulation).  tests/test_hip_parity.py::
 test_gradient_penalty_tangent_pass_matches_double_backward holds it to the double backward.
 """
-import math
 import os
 
 import torch
@@ -34,16 +35,7 @@ import hip_backend as hb
 import ops
 
 
-class _Ctx:
-    """Stand-in for an autograd ctx so that _DBlockFast.forward / .backward can be driven by hand."""
-
-    def __init__(self, needs):
-        self.needs_input_grad = needs
-        self.saved_tensors = ()
-        self.keep_gz = True
-
-    def save_for_backward(self, *t):
-        self.saved_tensors = t
+_X_ONLY = (True,) + (False,) * 9  # needs_input_grad of a block in the unit chain: the data gradient alone
 
 
 def supported(D, real):
@@ -105,13 +97,11 @@ class _DRealPenalty(torch.autograd.Function):
         blocks = [params[8 * i:8 * i + 8] for i in range(nb)]
         wf, bf, wfc, bfc = params[8 * nb:8 * nb + 4]
         # ---- pass 1: primal forward on the fused block kernels (what ops._DBlockFast.forward does under autograd)
-        x = real.detach()
-        ctxs = []
-        for (w_res, b_res, w1, b1, w2, b2, w3, b3), down in zip(blocks, layout):
-            c = _Ctx((True,) + (False,) * 9)
-            x = ops._DBlockFast.forward(c, x, w_res, b_res, w1, b1, w2, b2, w3, b3, down)
-            ctxs.append(c)
-        xf = x
+        xf = real.detach()
+        states = []
+        for p8, down in zip(blocks, layout):
+            xf, plan, saved = ops._dblock_forward(xf, p8, down)
+            states.append([plan, saved])
         yf = hb.conv2d_fwd(ops._cl(xf), wf, 1, 1, prec, bias=bf)
         bsz = yf.shape[0]
         flat = yf.reshape(bsz, -1).float()  # nn.Flatten of the logical NCHW tensor
@@ -119,11 +109,13 @@ class _DRealPenalty(torch.autograd.Function):
         # ---- pass 2: the unit data-gradient chain  u_b = dD(x_b)/dx_b; its pre-activation gradients are kept
         g_yf = ops._cl(wfc.detach().float().reshape(1, *yf.shape[1:]).expand(bsz, -1, -1, -1).contiguous())
         g = hb.conv2d_bwd_data(g_yf, wf, tuple(xf.shape), 1, 1, prec)
-        for c in reversed(ctxs):
-            g = ops._DBlockFast.backward(c, g)[0]
+        for st in reversed(states):
+            grads, gz = ops._dblock_backward(st[0], st[1], g, _X_ONLY)
+            g = grads[0]
+            st.append(gz)
         u = g.float().contiguous()
         norms = hb.rowwise_sumsq(u.reshape(bsz, -1)).sqrt()
-        ctx.layout, ctx.ctxs, ctx.nb = layout, ctxs, nb
+        ctx.states, ctx.nb = states, nb
         ctx.save_for_backward(u, norms, xf, g_yf, flat, *params)
         return out, norms
 
@@ -132,13 +124,9 @@ class _DRealPenalty(torch.autograd.Function):
     def backward(ctx, g_out, g_norm):
         prec = ops._PRECISION
         u, norms, xf, g_yf, flat = ctx.saved_tensors[:5]
-        params = ctx.saved_tensors[5:]
-        nb, layout, ctxs = ctx.nb, ctx.layout, ctx.ctxs
-        blocks = [params[8 * i:8 * i + 8] for i in range(nb)]
-        wf, bf, wfc, bfc = params[8 * nb:8 * nb + 4]
+        wf, bf, wfc, bfc = ctx.saved_tensors[5 + 8 * ctx.nb:9 + 8 * ctx.nb]
         bsz = u.shape[0]
         s = g_out.detach().float().reshape(bsz)  # dLoss / dD(x_b)
-        cinv = 1 / math.sqrt(2)
         # v = dLoss/du = g_norm_b * u_b / ||u_b||   (d||u|| / du = u / ||u||)
         # a sample whose input gradient is exactly zero: autograd's norm backward uses the subgradient 0 there (the
         # double backward this pass replaces), never 0 / 0
@@ -159,39 +147,17 @@ class _DRealPenalty(torch.autograd.Function):
         grads = []
         t = v
         # ---- pass 3 (tangent forward through the gated-linear network) and pass 4 (one weight gradient per conv)
-        for (w_res, b_res, w1, b1, w2, b2, w3, b3), down, c in zip(blocks, layout, ctxs):
-            x, xs, y1, y2, xb, _, _, _, _, m1, m2 = c.saved_tensors
-            downsample, s2d, cin, _ = c.cfg
-            gz3, gz2, gz1, alg = c.gz
-            wsc = cinv if alg else 1.0
-            if cin == 3:
-                t = hb.pad_rgb8(t) if (prec == hb.BF16_ACT and x.shape[1] == 8) else ops._cl(ops._pad_rgb(ops._cl(t), w1)[0])
-                extra = x.shape[1] - 3
-                w1p = torch.cat([w1, w1.new_zeros(w1.shape[0], extra, 3, 3)], dim=1)
-                wrp = torch.cat([w_res, w_res.new_zeros(w_res.shape[0], extra, 1, 1)], dim=1)
-            else:
-                t = ops._cl(t)
-                w1p, wrp = w1, w_res
-            if xs is None:
-                xs = x
+        for plan, sv, (gz3, gz2, gz1) in ctx.states:
+            x, xs, y1, xb, w2, w3 = sv.x, sv.xs, sv.y1, sv.xb, sv.w2, sv.w3
+            downsample, s2d, cin = plan.downsample, plan.s2d, plan.cin
+            wsc = plan.c if plan.alg else 1.0
+            t = ops._dblock_input(plan, t)
+            w1p, wrp, _, own_res = ops._dblock_weights(plan, sv.w1, sv.w_res)
             ts = hb.subsample2_fwd(t) if downsample else t
-            res_gemm = prec == hb.BF16_ACT and os.environ.get("STYLEX_RES_GEMM", "1") != "0"
-            res_t = hb.conv1x1_gemm_fwd(ts, wrp, None) if res_gemm else hb.conv2d_fwd(ts, wrp, 1, 0, prec)
-            a1 = _gated_conv3x3(t, w1p, y1, m1, prec)
-            a2 = _gated_conv3x3(a1, w2, y2, m2, prec)
-            n = w2.shape[0]
-            if downsample:
-                if s2d:
-                    ab = hb.blur3x3_s2d_fwd(a2)
-                    wf2, _ = hb.pack_weight_s2d(w3)
-                    t_out = hb.conv2d_fwd(ab, None, 1, 1, prec, residual=res_t, res_scale=cinv, packed=wf2,
-                                          w_shape=(w3.shape[0], 4 * n, 3, 3), s2d_c=n)
-                else:
-                    ab = hb.blur3x3_fwd(a2)
-                    t_out = hb.conv2d_fwd(ab, w3, 2, 1, prec, residual=res_t, res_scale=cinv)
-            else:
-                ab = None
-                t_out = (a2 + res_t) * cinv
+            res_t = ops._dblock_res_conv(plan, ts, wrp, own_res)
+            a1 = _gated_conv3x3(t, w1p, y1, sv.m1, prec)
+            a2 = _gated_conv3x3(a1, w2, sv.y2, sv.m2, prec)
+            t_out, ab = ops._dblock_tail(plan, a2, res_t, w3)
             # weight gradients: operand s_b * (primal activation) + (tangent activation), gradient = unit chain's
             gw1 = hb.conv2d_bwd_weight(operand(x, t), gz1, tuple(w1p.shape), 1, 1, prec)
             gw2 = hb.conv2d_bwd_weight(operand(y1, a1), gz2, tuple(w2.shape), 1, 1, prec)

@@ -21,6 +21,7 @@ object*.  The default and only product implementation is the HIP one below; it
 raises if the library or a GPU is missing.  ``tests/`` may install a CPU test
 double with ``use_impl`` to exercise the host logic without a GPU.
 """
+import collections
 import math
 
 import os
@@ -452,6 +453,21 @@ def _reducible(c):
     return c % 4 == 0 and c <= 1024
 
 
+def _grad_prologue(gy, y, lrelu, scale, want_gb):
+    """(gz, gb): gz = scale * lrelu'(y) * gy (gy itself when there is nothing to apply) and, with want_gb, its per-channel
+    sum in fp32 — one reduce launch where the channel count allows it, else ATen."""
+    want_dx = lrelu or scale != 1.0
+    if not (want_dx or want_gb):
+        return gy, None
+    if _reducible(gy.shape[1]):
+        gz, gb = hb.act_bwd_reduce(gy, y, lrelu, scale, want_dx=want_dx, want_sum=want_gb)
+        return (gz if want_dx else gy), gb
+    gz = hb.bias_act_bwd(gy, y) if lrelu else gy
+    if scale != 1.0:
+        gz = gz * scale
+    return gz, (gz.sum(dim=(0, 2, 3), dtype=torch.float32) if want_gb else None)
+
+
 class _ConvBiasActFast(torch.autograd.Function):
     """y = lrelu?( (conv(x, w) + bias + residual) * res_scale )"""
 
@@ -473,27 +489,11 @@ class _ConvBiasActFast(torch.autograd.Function):
     def backward(ctx, gy):
         x, w, y = ctx.saved_tensors
         stride, pad, lrelu, scale, has_bias, has_res = ctx.cfg
-        gy = _cl(gy)
-        gb = None
-        want_gb = has_bias and ctx.needs_input_grad[2]  # False in the generator phase (D frozen): no reduction launch
-        if _reducible(gy.shape[1]):
-            want_dx = lrelu or scale != 1.0
-            if want_dx or want_gb:
-                gz, gb = hb.act_bwd_reduce(gy, y, lrelu, scale, want_dx=want_dx, want_sum=want_gb)
-                if not want_dx:
-                    gz = gy
-            else:
-                gz = gy
-        else:
-            gz = hb.bias_act_bwd(gy, y) if lrelu else gy
-            if scale != 1.0:
-                gz = gz * scale
-            gb = gz.sum(dim=(0, 2, 3), dtype=torch.float32) if want_gb else None
+        # (no bias gradient in the generator phase, D frozen: no reduction launch)
+        gz, gb = _grad_prologue(_cl(gy), y, lrelu, scale, has_bias and ctx.needs_input_grad[2])
         with (hb.timing_pause() if ctx.untimed else _nullcontext()):
             gx = hb.conv2d_bwd_data(gz, w, tuple(x.shape), stride, pad, _PRECISION) if ctx.needs_input_grad[0] else None
             gw = hb.conv2d_bwd_weight(x, gz, tuple(w.shape), stride, pad, _PRECISION) if ctx.needs_input_grad[1] else None
-        if not ctx.needs_input_grad[2]:
-            gb = None
         return gx, gw, gb, (gz if has_res and ctx.needs_input_grad[3] else None), None, None, None, None
 
 
@@ -703,14 +703,7 @@ class _DownS2DFast(torch.autograd.Function):
         x2, w = ctx.saved_tensors
         scale, has_bias, has_res = ctx.cfg
         n, c = w.shape[0], w.shape[1]
-        gy = _cl(gy)
-        want_dx = scale != 1.0
-        want_gb = has_bias and ctx.needs_input_grad[2]
-        gz, gsum = gy, None
-        if want_dx or want_gb:
-            gz, gsum = hb.act_bwd_reduce(gy, None, False, scale, want_dx=want_dx, want_sum=want_gb)
-            if not want_dx:
-                gz = gy
+        gz, gb = _grad_prologue(_cl(gy), None, False, scale, has_bias and ctx.needs_input_grad[2])
         gx2 = gw = None
         if ctx.needs_input_grad[0]:
             _, wb2 = hb.pack_weight_s2d(w)
@@ -718,19 +711,222 @@ class _DownS2DFast(torch.autograd.Function):
                                      s2d_c=c)
         if ctx.needs_input_grad[1]:
             gw = hb.conv2d_bwd_weight_s2d(x2, gz, tuple(w.shape), _PRECISION)
-        gb = gsum if want_gb else None
         return gx2, gw, gb, (gz if has_res and ctx.needs_input_grad[3] else None), None
 
 
-def _fork_side(t):
-    """Companion stream for the 1x1 residual path of a fused DiscriminatorBlock (networks._side_stream), or None."""
-    # off by default: measured 699 vs 700 images/s with / without it (the fused block leaves too little idle time for
-    # a second stream to fill); STYLEX_DBLOCK_SIDE=1 switches it on for experiments
-    if os.environ.get("STYLEX_DBLOCK_SIDE", "0") != "1":
-        return None
-    import networks
+# The fused DiscriminatorBlock.  How a block runs is decided ONCE, by _dblock_plan in the forward; the backward and the
+# gradient-penalty tangent pass (gp_tangent.py) read the plan and the named saved state, never the environment.
+_DBlockPlan = collections.namedtuple(
+    "_DBlockPlan", "prec downsample cin pad extra res_gemm s2d fold_res mask1 mask2 alg wgrad_bias c")
+_DBlockSaved = collections.namedtuple("_DBlockSaved", "x xs y1 y2 xb m1 m2 w_res w1 w2 w3")
 
-    return networks._side_stream(t)
+
+def _dblock_plan(x_shape, x_dtype, x_cuda, w_shapes, downsample, prec, s2d_res_supported=hb.s2d_res_supported,
+                 blur_mask_ok=hb.blur_mask_ok):
+    """Every decision of one fused DiscriminatorBlock, from shapes, precision mode and the environment switches (read per
+    call: tests toggle them).  w_shapes: of (w_res, w1, w2, w3), w3's None without a stride-2 tail.  The two probes are
+    arguments so that the rules can be evaluated without the kernel library."""
+    def on(name):
+        return os.environ.get(name, "1") != "0"
+
+    b, cin, h, w = x_shape
+    n_res, n2 = w_shapes[0][0], w_shapes[2][0]
+    downsample, bf16 = bool(downsample), prec == hb.BF16_ACT
+    # RGB input: zero-padded to one 16-byte channel slot (8 bf16 / 4 fp32 channels), gradients are sliced back.  The bf16
+    # mode casts, lays out and pads in ONE pass (pad_rgb8); STYLEX_PAD_RGB=0 and the other modes concatenate (_pad_rgb)
+    pad, extra = None, 0
+    if cin == 3:
+        rgb8 = bf16 and x_cuda and x_dtype in (torch.float32, torch.bfloat16) and on("STYLEX_PAD_RGB")
+        pad, extra = ("pad_rgb8", 5) if rgb8 else ("_pad_rgb", 5 if bf16 else 1)
+    # the 1x1 conv of the residual path is a plain GEMM: hipBLASLt in the bf16 mode (2-3x the generic kernel)
+    res_gemm = bf16 and on("STYLEX_RES_GEMM")
+    # the stride-2 conv as a 3x3/s1 conv over the space-to-depth image of the blur output (LDS-DMA kernels)
+    s2d = downsample and prec != hb.F32 and n2 % 64 == 0 and h % 2 == 0 and w % 2 == 0 and w // 2 >= 16 and h // 2 >= 16
+    # Such blocks take the residual conv as a second K segment of that launch (hb.conv2d_s2d_res_fwd): no GEMM, no bf16
+    # `res` tensor written and read back (round 4; STYLEX_RES_FOLD=0 = the separate GEMM).  Only the s2d tail consumes it.
+    fold_res = (s2d and res_gemm and (cin + extra) % 8 == 0 and on("STYLEX_RES_FOLD")
+                and bool(s2d_res_supported((b, 4 * n2, h // 2, w // 2), n_res, n2, cin + extra)))
+    # Activation bit masks: the backward needs y2 ONLY for its sign (the LeakyReLU derivative fused into the blur adjoint)
+    # and y1 for its sign plus as the weight-gradient operand; where the forward kernel can write the sign bits alongside
+    # (1/16 of the bytes) the gated backward passes read those instead of the tensors, and y2 is not kept for the backward
+    # at all.  STYLEX_GATE_MASK=0: gate on the tensors.
+    # (measured per launch at B=64, tools/bench_masks.py: gated data gradient 64->64 @256^2 .534 -> .445 ms, gated blur
+    # adjoint .323 -> .273, 128 @128^2 .356 -> .327 / .159 -> .141; writing the mask costs the forward 0 - .012 ms;
+    # at 64^2 and below the saving no longer covers that, so the masks are used from 128^2 up)
+    mask1 = bf16 and on("STYLEX_GATE_MASK") and h * w >= int(os.environ.get("STYLEX_GATE_MASK_MIN_PIXELS", 128 * 128))
+    mask2 = mask1 and s2d and bool(blur_mask_ok((b, n2, h, w), hb.act_dtype(prec)))
+    # (. + res) / sqrt(2).  In the bf16 modes the constant c never touches the activation gradient: it is folded into
+    # the packed data-gradient operands (c*w3, c*w_res) and into the (small) weight / bias gradients, which removes one
+    # full pass over the block's output gradient; the fp32 parity mode scales explicitly.
+    alg = downsample and prec != hb.F32
+    return _DBlockPlan(prec, downsample, cin, pad, extra, res_gemm, s2d, fold_res, mask1, mask2, alg,
+                       on("STYLEX_WGRAD_BIAS"), 1 / math.sqrt(2))
+
+
+def _dblock_input(plan, x):
+    """The block's input, or a tangent of it, as the kernels read it: activation dtype, channels_last, RGB padded."""
+    if plan.pad == "pad_rgb8":
+        return hb.pad_rgb8(x.detach())
+    x = _cl(_act(x))
+    if plan.pad:
+        x = _cl(torch.cat([x, x.new_zeros(x.shape[0], plan.extra, x.shape[2], x.shape[3])], dim=1))
+    return x
+
+
+def _dblock_weights(plan, w1, w_res):
+    """(w1p, wrp, owner1, owner_res): the weights that read the (padded) input, and the Parameters under whose
+    modification stamp the operand copies of a padded weight are cached (None: the weight is the Parameter itself).
+    The padded weights are cached too (they used to be rebuilt — zeros, cat, pack, cast — in every pass of block 0)."""
+    if not plan.pad:
+        return w1, w_res, None, None
+    return hb.pad_in_channels(w1, plan.extra), hb.pad_in_channels(w_res, plan.extra), w1, w_res
+
+
+def _owned_pack(w, owner, fwd, prec):
+    """conv keyword arguments that hand the launch a padded weight's operand pack, cached under its Parameter."""
+    if not isinstance(owner, torch.nn.Parameter):
+        return {}
+    return dict(packed=hb.pack_weight(w, fwd, not fwd, prec, owner=owner)[0 if fwd else 1], w_shape=tuple(w.shape))
+
+
+def _dblock_res_conv(plan, xs, wrp, owner, bias=None):
+    """The 1x1 residual conv over the (gathered) input: GEMM or generic kernel."""
+    if plan.res_gemm:
+        return hb.conv1x1_gemm_fwd(xs, wrp, bias, owner=owner)
+    return hb.conv2d_fwd(xs, wrp, 1, 0, plan.prec, bias=bias)
+
+
+def _dblock_tail(plan, y2, res, w3, b3=None, fold=None):
+    """(out, xb): blur, stride-2 conv and the merge with the residual path, (conv3x3_s2(blur(y2)) + b3 + res) / sqrt(2);
+    without a stride-2 tail (y2 + res) / sqrt(2).  fold = (xs, wrp, owner, b_res) when plan.fold_res: res is computed
+    inside the launch."""
+    c, prec = plan.c, plan.prec
+    if not plan.downsample:
+        return (y2 + res) * c, None
+    if not plan.s2d:
+        xb = hb.blur3x3_fwd(y2)
+        return hb.conv2d_fwd(xb, w3, 2, 1, prec, bias=b3, residual=res, res_scale=c), xb
+    n = y2.shape[1]
+    xb = hb.blur3x3_s2d_fwd(y2)
+    wf2, _ = hb.pack_weight_s2d(w3)
+    if fold is None:
+        return hb.conv2d_fwd(xb, None, 1, 1, prec, bias=b3, residual=res, res_scale=c, packed=wf2,
+                             w_shape=(w3.shape[0], 4 * n, 3, 3), s2d_c=n), xb
+    xs, wrp, owner, b_res = fold
+    bsum = hb.cached_vector("sum32", lambda a, b: a.float() + b.float(), b3, b_res)
+    return hb.conv2d_s2d_res_fwd(xb, wf2, xs, hb._bf16_matrix(wrp, owner=owner), bsum, w3.shape[0], n, c), xb
+
+
+def _dblock_forward(x, params, downsample):
+    """(out, plan, saved) of one block; params = (w_res, b_res, w1, b1, w2, b2, w3, b3), w3 / b3 None without a tail."""
+    w_res, b_res, w1, b1, w2, b2, w3, b3 = params
+    plan = _dblock_plan(tuple(x.shape), x.dtype, x.is_cuda, [None if p is None else tuple(p.shape) for p in params[::2]],
+                        downsample, _PRECISION)
+    prec = plan.prec
+    x = _dblock_input(plan, x)
+    w1p, wrp, own1, own_res = _dblock_weights(plan, w1, w_res)
+    xs = hb.subsample2_fwd(x) if plan.downsample else x
+    res = None if plan.fold_res else _dblock_res_conv(plan, xs, wrp, own_res, b_res)
+    y1 = hb.conv2d_fwd(x, w1p, 1, 1, prec, bias=b1, lrelu=True, want_mask=plan.mask1, **_owned_pack(w1p, own1, True, prec))
+    y1, m1 = y1 if plan.mask1 else (y1, None)
+    y2 = hb.conv2d_fwd(y1, w2, 1, 1, prec, bias=b2, lrelu=True, want_mask=plan.mask2)
+    y2, m2 = y2 if plan.mask2 else (y2, None)
+    out, xb = _dblock_tail(plan, y2, res, w3, b3, (xs, wrp, own_res, b_res) if plan.fold_res else None)
+    return out, plan, _DBlockSaved(x, xs, y1, y2 if m2 is None else None, xb, m1, m2, w_res, w1, w2, w3)
+
+
+def _dblock_backward(plan, saved, g_out, need):
+    """((gx, gw_res, gb_res, gw1, gb1, gw2, gb2, gw3, gb3), (gz3, gz2, gz1)): every gradient that `need` (the block's
+    needs_input_grad) asks for, and the three pre-activation gradients (gz3 without its 1/sqrt(2) when plan.alg)."""
+    x, xs, y1, y2, xb, m1, m2, w_res, w1, w2, w3 = saved
+    prec, c, cin, alg = plan.prec, plan.c, plan.cin, plan.alg
+    want_x = need[0]
+    want_b = need[2] or need[4] or need[6] or need[8]  # bias gradients (False for the frozen D of the G phase)
+    want_w = need[1] or need[3] or need[5] or need[7]
+    g_out = _cl(g_out)
+    if alg:
+        gz3, gsum3 = g_out, (_channel_sum(g_out, c) if want_b else None)  # the sum with its 1/sqrt(2)
+    else:
+        gz3, gsum3 = _grad_prologue(g_out, None, False, c, want_b)
+    # factor owed by the gradients computed from the unscaled gz3: the out_scale of their reduce launches (round 5: it was
+    # a multi-tensor multiply of 26 us per block, 0.47 ms per step)
+    wsc = c if alg else 1.0
+    w1p, wrp, own1, own_res = _dblock_weights(plan, w1, w_res)
+    gw3 = None
+    if plan.downsample:
+        n = w2.shape[0]
+        if plan.s2d:
+            _, wb2 = hb.pack_weight_s2d(w3, scale=c if alg else None)
+            gxb = hb.conv2d_bwd_data(gz3, None, tuple(xb.shape), 1, 1, prec, packed=wb2, w_shape=(w3.shape[0], 4 * n, 3, 3),
+                                     s2d_c=n)
+        else:
+            wb3 = hb.pack_weight(w3, False, True, prec, scale=c)[1] if alg else None
+            gxb = hb.conv2d_bwd_data(gz3, w3, tuple(xb.shape), 2, 1, prec, packed=wb3, w_shape=tuple(w3.shape))
+        if want_w:
+            a3 = _gacc_get(w3)
+            if plan.s2d:
+                gw3 = hb.conv2d_bwd_weight_s2d(xb, gz3, tuple(w3.shape), prec, out_scale=wsc, accumulate_into=a3)
+            else:
+                gw3 = hb.conv2d_bwd_weight(xb, gz3, tuple(w3.shape), 2, 1, prec, out_scale=wsc, accumulate_into=a3)
+            if a3 is None and need[7]:
+                _gacc_put(w3, gw3)
+        # blur adjoint + LeakyReLU derivative of y2, one pass
+        gz2 = hb.blur3x3_s2d_bwd(gxb, gate=y2, gate_mask=m2) if plan.s2d else hb.blur3x3_bwd_gate(gxb, y2)
+    else:
+        gz2 = hb.bias_act_bwd(gz3, y2)
+    # bias gradients = per-channel sums of gz2 / gz1: taken from the weight-gradient kernel (which stages those
+    # tensors anyway) where it can, else a read-only reduction pass
+    fuse_b = want_b and want_w and plan.wgrad_bias
+
+    def layer_grads(w, w_shape, xin, gz, acc, need_w, need_b):
+        """(gw, gb) of a 3x3 layer; acc: its gradients may be added into / named as the first use's (_gacc_*)."""
+        gw = gb = None
+        if want_w:
+            aw = _gacc_get(w) if acc else None
+            ab = _gacc_get(w, "b") if aw is not None else None
+            gw = hb.conv2d_bwd_weight(xin, gz, w_shape, 1, 1, prec, want_bias_sum=fuse_b, accumulate_into=aw,
+                                      accumulate_bias_into=ab)
+            if fuse_b:
+                gw, gb = gw
+                if gb is True:  # added into the first use's bias gradient
+                    return gw, None
+            if aw is None and acc:  # (only what this node really hands to the engine may be named)
+                if need_w:
+                    _gacc_put(w, gw)
+                if need_b:
+                    _gacc_put(w, gb, "b")
+        if want_b and gb is None:
+            gb = _channel_sum(gz)
+        return gw, gb
+
+    gw2, gb2 = layer_grads(w2, tuple(w2.shape), y1, gz2, True, need[5], need[6])
+    gz1 = hb.conv2d_bwd_data(gz2, w2, tuple(y1.shape), 1, 1, prec, gate=y1, gate_mask=m1)  # + LeakyReLU derivative of y1
+    # (the padded-RGB block returns a slice of its gradients: nothing of it is accumulated into or named)
+    gw1, gb1 = layer_grads(w1, tuple(w1p.shape), x, gz1, cin != 3, need[3], need[4])
+    gx = gw_res = None
+    if want_x:
+        gx = hb.conv2d_bwd_data(gz1, w1p, tuple(x.shape), 1, 1, prec, **_owned_pack(w1p, own1, False, prec))
+    if want_w:
+        a_res = _gacc_get(w_res) if cin != 3 else None
+        gw_res = hb.conv2d_bwd_weight(xs, gz3, tuple(wrp.shape), 1, 0, prec, out_scale=wsc, accumulate_into=a_res)
+        if a_res is None and cin != 3 and need[1]:
+            _gacc_put(w_res, gw_res)
+        if cin == 3:
+            gw1, gw_res = gw1[:, :3].contiguous(), gw_res[:, :3].contiguous()
+    if want_x:
+        if plan.res_gemm:  # [M, N] x [N, C] on hipBLASLt, the 1/sqrt(2) folded into the bf16 weight copy as below
+            gxs = hb.conv1x1_gemm_bwd_data(gz3, wrp, scale=c if alg else None, owner=own_res)
+        else:
+            wbr = hb.pack_weight(wrp, False, True, prec, scale=c)[1] if alg else None
+            gxs = hb.conv2d_bwd_data(gz3, wrp, tuple(xs.shape), 1, 0, prec, packed=wbr, w_shape=tuple(wrp.shape))
+        if plan.downsample:
+            hb.add_at_even_(gx, gxs)  # adjoint of the even-pixel gather, summed in place
+        else:
+            gx += gxs
+        if cin == 3:
+            gx = gx[:, :3]
+    # the per-channel sum of the output gradient is the bias gradient of BOTH conv_res and the down conv
+    return (gx, gw_res, gsum3, gw1, gb1, gw2, gb2, gw3, gsum3 if plan.downsample else None), (gz3, gz2, gz1)
 
 
 class _DBlockFast(torch.autograd.Function):
@@ -744,261 +940,21 @@ class _DBlockFast(torch.autograd.Function):
     activation-derivative pass over the two largest tensors of the block), the bias gradient of the residual conv and
     of the down conv is the same reduction, and the gradient of the 1x1/stride-2 path is added into the 3x3 path's
     input gradient at the even pixels in place (no zero-inserted tensor, no full-resolution add).  First-order only
-    (used when no double backward can be requested, see set_fast)."""
+    (used when no double backward can be requested, see set_fast).  The work is in _dblock_forward / _dblock_backward,
+    which gp_tangent drives directly; this class only saves and restores their state."""
 
     @staticmethod
     def forward(ctx, x, w_res, b_res, w1, b1, w2, b2, w3, b3, downsample):
-        c = 1 / math.sqrt(2)
-        cin = x.shape[1]
-        if (cin == 3 and _PRECISION == hb.BF16_ACT and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)
-                and os.environ.get("STYLEX_PAD_RGB", "1") != "0"):
-            # RGB input, bf16 mode: cast + channels_last + zero-pad to one 16-byte channel slot in ONE pass
-            x = hb.pad_rgb8(x.detach())
-            # padded weights and their operand packs: cached per parameter version (they used to be rebuilt — zeros,
-            # cat, pack, cast — in every forward and backward of block 0: ~50 launches per train() call)
-            w1p, wrp = hb.pad_in_channels(w1, 5), hb.pad_in_channels(w_res, 5)
-        elif cin == 3:  # RGB input: pad to one 16-byte channel slot (see _pad_rgb); gradients are sliced back
-            x = _cl(_act(x))
-            x, w1p, _ = _pad_rgb(x, w1)
-            x = _cl(x)
-            wrp = torch.cat([w_res, w_res.new_zeros(w_res.shape[0], x.shape[1] - 3, 1, 1)], dim=1)
-        else:
-            x = _cl(_act(x))
-            w1p, wrp = w1, w_res
-        # the 1x1 residual path (even-pixel gather + small GEMM) is independent of the two 3x3 convs until the merge:
-        # companion HIP stream, joined before the kernel that merges
-        side = _fork_side(x)
-        # the 1x1 conv of the residual path is a plain GEMM: hipBLASLt in the bf16 mode (2-3x the generic kernel)
-        res_gemm = _PRECISION == hb.BF16_ACT and os.environ.get("STYLEX_RES_GEMM", "1") != "0"
-        conv_res = (lambda t: hb.conv1x1_gemm_fwd(t, wrp if cin == 3 else w_res, b_res,
-                                                  owner=w_res if cin == 3 else None)) if res_gemm else (
-            lambda t: hb.conv2d_fwd(t, wrp, 1, 0, _PRECISION, bias=b_res))
-        # Blocks whose stride-2 conv runs on the LDS-DMA space-to-depth kernel take the residual conv as a second K segment
-        # of that launch (hb.conv2d_s2d_res_fwd): no GEMM, no bf16 `res` tensor written and read back (round 4;
-        # STYLEX_RES_FOLD=0 = the separate GEMM)
-        n2_, h2_, w2_ = w2.shape[0], x.shape[2], x.shape[3]
-        fold_res = (bool(downsample) and _PRECISION == hb.BF16_ACT and res_gemm and h2_ % 2 == 0 and w2_ % 2 == 0
-                    and n2_ % 64 == 0 and x.shape[1] % 8 == 0 and os.environ.get("STYLEX_RES_FOLD", "1") != "0"
-                    and hb.s2d_res_supported((x.shape[0], 4 * n2_, h2_ // 2, w2_ // 2), w_res.shape[0], n2_, x.shape[1]))
-        res = None
-        if fold_res:
-            xs = hb.subsample2_fwd(x)
-            side = None
-        elif side is None:
-            xs = hb.subsample2_fwd(x) if downsample else x
-            res = conv_res(xs)
-        else:
-            main = torch.cuda.current_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                xs = hb.subsample2_fwd(x) if downsample else x
-                res = conv_res(xs)
-            x.record_stream(side)
-        # Activation bit masks: the backward needs y2 ONLY for its sign (the LeakyReLU derivative fused into the blur
-        # adjoint) and y1 for its sign plus as the weight-gradient operand; where the forward kernel can write the sign
-        # bits alongside (1/16 of the bytes) the gated backward passes read those instead of the tensors, and y2 is not
-        # kept for the backward at all.  STYLEX_GATE_MASK=0: gate on the tensors.
-        n2, h2, wd2 = w2.shape[0], x.shape[2], x.shape[3]
-        s2d_next = bool(downsample) and (_PRECISION != hb.F32 and n2 % 64 == 0 and h2 % 2 == 0 and wd2 % 2 == 0
-                                         and wd2 // 2 >= 16 and h2 // 2 >= 16)
-        # (measured per launch at B=64, tools/bench_masks.py: gated data gradient 64->64 @256^2 .534 -> .445 ms, gated blur
-        # adjoint .323 -> .273, 128 @128^2 .356 -> .327 / .159 -> .141; writing the mask costs the forward 0 - .012 ms;
-        # at 64^2 and below the saving no longer covers that, so the masks are used from 128^2 up)
-        use_m = (_PRECISION == hb.BF16_ACT and os.environ.get("STYLEX_GATE_MASK", "1") != "0"
-                 and h2 * wd2 >= int(os.environ.get("STYLEX_GATE_MASK_MIN_PIXELS", 128 * 128)))
-        pk1 = dict(packed=hb.pack_weight(w1p, True, False, _PRECISION, owner=w1)[0], w_shape=tuple(w1p.shape)) \
-            if (cin == 3 and w1p is not w1 and isinstance(w1, torch.nn.Parameter)) else {}
-        y1, m1 = hb.conv2d_fwd(x, w1p, 1, 1, _PRECISION, bias=b1, lrelu=True, want_mask=True, **pk1) if use_m else (
-            hb.conv2d_fwd(x, w1p, 1, 1, _PRECISION, bias=b1, lrelu=True, **pk1), None)
-        want_m2 = use_m and s2d_next and hb.blur_mask_ok((x.shape[0], n2, h2, wd2), x.dtype)
-        y2, m2 = hb.conv2d_fwd(y1, w2, 1, 1, _PRECISION, bias=b2, lrelu=True, want_mask=True) if want_m2 else (
-            hb.conv2d_fwd(y1, w2, 1, 1, _PRECISION, bias=b2, lrelu=True), None)
-        s2d, xb = False, None
-        def join():
-            if side is not None:
-                torch.cuda.current_stream().wait_stream(side)
-                res.record_stream(torch.cuda.current_stream())
-                xs.record_stream(torch.cuda.current_stream())
-
-        if downsample:
-            n, h, w = y2.shape[1], y2.shape[2], y2.shape[3]
-            s2d = (_PRECISION != hb.F32 and n % 64 == 0 and h % 2 == 0 and w % 2 == 0 and w // 2 >= 16 and h // 2 >= 16)
-            if s2d:
-                xb = hb.blur3x3_s2d_fwd(y2)
-                join()
-                wf2, _ = hb.pack_weight_s2d(w3)
-                if fold_res:
-                    wm = hb._bf16_matrix(wrp if cin == 3 else w_res, owner=w_res if cin == 3 else None)
-                    bsum = hb.cached_vector("sum32", lambda a, b: a.float() + b.float(), b3, b_res)
-                    out = hb.conv2d_s2d_res_fwd(xb, wf2, xs, wm, bsum, w3.shape[0], n, c)
-                else:
-                    out = hb.conv2d_fwd(xb, None, 1, 1, _PRECISION, bias=b3, residual=res, res_scale=c, packed=wf2,
-                                        w_shape=(w3.shape[0], 4 * n, 3, 3), s2d_c=n)
-            else:
-                xb = hb.blur3x3_fwd(y2)
-                join()
-                out = hb.conv2d_fwd(xb, w3, 2, 1, _PRECISION, bias=b3, residual=res, res_scale=c)
-        else:
-            join()
-            out = (y2 + res) * c
-        assert m2 is None or s2d
-        ctx.save_for_backward(x, xs if downsample else None, y1, y2 if m2 is None else None, xb, w_res, w1, w2, w3, m1, m2)
-        ctx.y2_shape = tuple(y2.shape)
-        ctx.cfg = (bool(downsample), s2d, cin, c)
+        out, ctx.plan, saved = _dblock_forward(x, (w_res, b_res, w1, b1, w2, b2, w3, b3), downsample)
+        ctx.save_for_backward(*saved)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_out):
-        x, xs, y1, y2, xb, w_res, w1, w2, w3, m1, m2 = ctx.saved_tensors
-        downsample, s2d, cin, c = ctx.cfg
-        if xs is None:
-            xs = x
         need = ctx.needs_input_grad
-        want_x = need[0]
-        want_b = need[2] or need[4] or need[6] or need[8]  # bias gradients (False for the frozen D of the G phase)
-        want_w = need[1] or need[3] or need[5] or need[7]
-        g_out = _cl(g_out)
-        prec = _PRECISION
-        gw_res = gb_res = gw1 = gb1 = gw2 = gb2 = gw3 = gb3 = gx = None
-        # (. + res) / sqrt(2).  In the bf16 modes the constant c never touches the activation gradient: it is folded
-        # into the packed data-gradient operands (c*w3, c*w_res) and into the (small) weight / bias gradients, which
-        # removes one full pass over the block's output gradient; the fp32 parity mode scales explicitly.
-        alg = downsample and prec != hb.F32
-        if alg:
-            gz3 = g_out
-            gsum3 = _channel_sum(g_out, c) if want_b else None  # with its 1/sqrt(2)
-        elif _reducible(g_out.shape[1]):
-            gz3, gsum3 = hb.act_bwd_reduce(g_out, None, False, c, want_dx=True, want_sum=want_b)
-        else:
-            gz3 = g_out * c
-            gsum3 = gz3.sum(dim=(0, 2, 3), dtype=torch.float32) if want_b else None
-        wsc = c if alg else 1.0  # factor owed by the gradients computed from the unscaled gz3: the reduce launches' out_scale
-        gb_res = gsum3  # the per-channel sum is the bias gradient of BOTH conv_res and the down conv
-        if cin == 3:  # x was saved padded; only the weights need padding again
-            extra = x.shape[1] - 3
-            w1p, wrp = hb.pad_in_channels(w1, extra), hb.pad_in_channels(w_res, extra)
-        else:
-            w1p, wrp = w1, w_res
-        # residual path (1x1 weight gradient + data gradient on the quarter-size tensor): companion stream, joined
-        # before its results are used at the end
-        side_bwd, side_out, main = _fork_side(g_out), None, torch.cuda.current_stream() if g_out.is_cuda else None
-        res_gemm = prec == hb.BF16_ACT and os.environ.get("STYLEX_RES_GEMM", "1") != "0"
-
-        def res_dgrad():
-            if res_gemm:  # [M, N] x [N, C] on hipBLASLt, the 1/sqrt(2) folded into the bf16 weight copy as below
-                return hb.conv1x1_gemm_bwd_data(gz3, wrp if cin == 3 else w_res, scale=c if alg else None,
-                                                owner=w_res if cin == 3 else None)
-            wbr = hb.pack_weight(wrp, False, True, prec, scale=c)[1] if alg else None
-            return hb.conv2d_bwd_data(gz3, wrp, tuple(xs.shape), 1, 0, prec, packed=wbr, w_shape=tuple(wrp.shape))
-
-        a_res = _gacc_get(w_res) if (want_w and cin != 3) else None
-        if side_bwd is not None:
-            side_bwd.wait_stream(main)
-            with torch.cuda.stream(side_bwd):
-                s_gw = s_gx = None
-                if want_w:
-                    s_gw = hb.conv2d_bwd_weight(xs, gz3, tuple(wrp.shape), 1, 0, prec, out_scale=wsc, accumulate_into=a_res)
-                if want_x:
-                    s_gx = res_dgrad()
-                side_out = (s_gw, s_gx)
-            gz3.record_stream(side_bwd)
-            xs.record_stream(side_bwd)
-        if downsample:
-            gb3 = gsum3
-            n = ctx.y2_shape[1]
-            if s2d:
-                _, wb2 = hb.pack_weight_s2d(w3, scale=c if alg else None)
-                gxb = hb.conv2d_bwd_data(gz3, None, tuple(xb.shape), 1, 1, prec, packed=wb2, w_shape=(w3.shape[0], 4 * n, 3, 3),
-                                         s2d_c=n)
-                if want_w:
-                    a3 = _gacc_get(w3)
-                    gw3 = hb.conv2d_bwd_weight_s2d(xb, gz3, tuple(w3.shape), prec, out_scale=wsc, accumulate_into=a3)
-                    if a3 is None and need[7]:
-                        _gacc_put(w3, gw3)
-                gz2 = hb.blur3x3_s2d_bwd(gxb, gate=y2, gate_mask=m2)  # blur adjoint + LeakyReLU derivative of y2, one pass
-            else:
-                wb3 = hb.pack_weight(w3, False, True, prec, scale=c)[1] if alg else None
-                gxb = hb.conv2d_bwd_data(gz3, w3, tuple(xb.shape), 2, 1, prec, packed=wb3, w_shape=tuple(w3.shape))
-                if want_w:
-                    a3 = _gacc_get(w3)
-                    gw3 = hb.conv2d_bwd_weight(xb, gz3, tuple(w3.shape), 2, 1, prec, out_scale=wsc, accumulate_into=a3)
-                    if a3 is None and need[7]:
-                        _gacc_put(w3, gw3)
-                gz2 = hb.blur3x3_bwd_gate(gxb, y2)
-        else:
-            gz2 = hb.bias_act_bwd(gz3, y2)
-        # bias gradients = per-channel sums of gz2 / gz1: taken from the weight-gradient kernel (which stages those
-        # tensors anyway) where it can, else a read-only reduction pass
-        fuse_b = want_b and want_w and os.environ.get("STYLEX_WGRAD_BIAS", "1") != "0"
-        acc_b2 = False
-        if want_w:
-            a2w, a2b = _gacc_get(w2), _gacc_get(w2, "b")
-            gw2 = hb.conv2d_bwd_weight(y1, gz2, tuple(w2.shape), 1, 1, prec, want_bias_sum=fuse_b, accumulate_into=a2w,
-                                       accumulate_bias_into=a2b if a2w is not None else None)
-            if fuse_b:
-                gw2, gb2 = gw2
-                if gb2 is True:  # added into the first use's bias gradient
-                    gb2, acc_b2 = None, True
-            if a2w is None:  # (only what this node really hands to the engine may be named)
-                if need[5]:
-                    _gacc_put(w2, gw2)
-                if need[6]:
-                    _gacc_put(w2, gb2, "b")
-        if want_b and gb2 is None and not acc_b2:
-            gb2 = _channel_sum(gz2)
-        gz1 = hb.conv2d_bwd_data(gz2, w2, tuple(y1.shape), 1, 1, prec, gate=y1, gate_mask=m1)  # + LeakyReLU derivative of y1
-        if getattr(ctx, "keep_gz", False):  # hand-driven backward (gp_tangent): the pre-activation gradients are reused
-            ctx.gz = (gz3, gz2, gz1, alg)
-        gxs = None
-        acc_b1 = False
-        if want_w:
-            a1w = _gacc_get(w1) if cin != 3 else None  # (the padded-RGB block returns a slice of its gradient)
-            a1b = _gacc_get(w1, "b") if a1w is not None else None
-            gw1 = hb.conv2d_bwd_weight(x, gz1, tuple(w1p.shape), 1, 1, prec, want_bias_sum=fuse_b, accumulate_into=a1w,
-                                       accumulate_bias_into=a1b)
-            if fuse_b:
-                gw1, gb1 = gw1
-                if gb1 is True:
-                    gb1, acc_b1 = None, True
-            if a1w is None and cin != 3:
-                if need[3]:
-                    _gacc_put(w1, gw1)
-                if need[4]:
-                    _gacc_put(w1, gb1, "b")
-        if want_b and gb1 is None and not acc_b1:
-            gb1 = _channel_sum(gz1)
-        if want_x:
-            pk1 = dict(packed=hb.pack_weight(w1p, False, True, prec, owner=w1)[1], w_shape=tuple(w1p.shape)) \
-                if (cin == 3 and isinstance(w1, torch.nn.Parameter)) else {}
-            gx = hb.conv2d_bwd_data(gz1, w1p, tuple(x.shape), 1, 1, prec, **pk1)
-        if side_bwd is not None:  # join: the residual-path gradients were issued on the companion stream above
-            gw_res, gxs = side_out
-            main.wait_stream(side_bwd)
-            for t in (gw_res, gxs):
-                if t is not None:
-                    t.record_stream(main)
-        else:
-            if want_w:
-                gw_res = hb.conv2d_bwd_weight(xs, gz3, tuple(wrp.shape), 1, 0, prec, out_scale=wsc, accumulate_into=a_res)
-            if want_x:
-                gxs = res_dgrad()
-        # (round 5: the 1/sqrt(2) owed by gw_res, gw3 and gsum3 rides their reduce launches — it was a multi-tensor multiply
-        # of 26 us per block, 0.47 ms per step)
-        if want_w and a_res is None and cin != 3 and need[1]:
-            _gacc_put(w_res, gw_res)
-        if want_w and cin == 3:
-            gw1, gw_res = gw1[:, :3].contiguous(), gw_res[:, :3].contiguous()
-        if want_x:
-            if downsample:
-                hb.add_at_even_(gx, gxs)  # adjoint of the even-pixel gather, summed in place
-            else:
-                gx += gxs
-            if cin == 3:
-                gx = gx[:, :3]
-        return (gx, gw_res if need[1] else None, gb_res if need[2] else None, gw1 if need[3] else None,
-                gb1 if need[4] else None, gw2 if need[5] else None, gb2 if need[6] else None,
-                gw3 if need[7] else None, gb3 if need[8] else None, None)
+        grads, _ = _dblock_backward(ctx.plan, _DBlockSaved(*ctx.saved_tensors), g_out, need)
+        return tuple(g if wanted else None for g, wanted in zip(grads, need)) + (None,)
 
 
 # Gradient accumulation inside the weight-gradient launches (round 5).  A parameter used by several fast-path nodes of ONE
