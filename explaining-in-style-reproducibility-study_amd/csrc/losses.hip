@@ -1,6 +1,8 @@
 // losses.hip — the scalar loss reductions of the train step, each as ONE forward and ONE backward launch
 // instead of the 5-10 ATen launches of its torch composition:
 //   hinge            /root/reference/stylex/stylex_train.py:382-387   mean(relu(1 + real) + relu(1 - fake)),  fake.mean()
+//   hinge, relativistic  :1338-1342 (rel_disc_loss)                   the hinge of real - mean(fake), fake - mean(real)
+//   top-k mean       :1401-1407 (top_k_training)                      mean of the k smallest values
 //   pl_lengths       :306-316 (:316)                                  sqrt(mean_l(sum_d(g^2)))  per sample
 //   kl_logits        :421-438 + KLDivLoss(batchmean, log_target) :406 sum_b sum_k p_real (log p_real - log p_fake) / B
 //   l1_mean          nn.L1Loss :404-405 (used at :415-418)            mean(|a - b|)
@@ -71,6 +73,97 @@ __global__ __launch_bounds__(LT) void hinge_bwd_kernel(const float* real, const 
     } else if (gfake) {
         gfake[i] = g;
     }
+}
+
+// ---- relativistic average hinge (rel_disc_loss): ONE block, three fixed-order passes -----------------------------------
+//   out = mean_i(relu(1 + real_i - mean(fake)) + relu(1 - fake_i + mean(real)))
+// With a_i = [1 + real_i - mean(fake) > 0] and b_i = [1 - fake_i + mean(real) > 0] (relu'(0) = 0, as above):
+//   d out / d real_i = (a_i + mean(b)) / n,   d out / d fake_i = -(b_i + mean(a)) / n      (both means carry gradient)
+// every thread ends up with the block's sum (the order of the additions is fixed)
+__device__ __forceinline__ float block_sum_all(float v, float* sm) {
+    v = wave_sum(v);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();  // sm may still be read from a previous call
+    if (lane == 0) sm[wave] = v;
+    __syncthreads();
+    float r = 0.f;
+#pragma unroll
+    for (int w = 0; w < LT / 64; ++w) r += sm[w];
+    return r;
+}
+
+__device__ __forceinline__ void rel_means(const float* real, const float* fake, long n, float* sm, float& mr, float& mf) {
+    float sr = 0.f, sf = 0.f;
+    for (long i = threadIdx.x; i < n; i += LT) {
+        sr += real[i];
+        sf += fake[i];
+    }
+    mr = block_sum_all(sr, sm) / (float)n;
+    mf = block_sum_all(sf, sm) / (float)n;
+}
+
+__global__ __launch_bounds__(LT) void hinge_rel_fwd_kernel(const float* real, const float* fake, float* out, long n) {
+    __shared__ float sm[LT / 64];
+    float mr, mf;
+    rel_means(real, fake, n, sm, mr, mf);
+    float s = 0.f;
+    for (long i = threadIdx.x; i < n; i += LT) s += fmaxf(1.f + (real[i] - mf), 0.f) + fmaxf(1.f - (fake[i] - mr), 0.f);
+    s = block_sum_all(s, sm);
+    if (threadIdx.x == 0) out[0] = s / (float)n;
+}
+
+__global__ __launch_bounds__(LT) void hinge_rel_bwd_kernel(const float* real, const float* fake, const float* gout, float* greal,
+                                                            float* gfake, long n) {
+    __shared__ float sm[LT / 64];
+    float mr, mf;
+    rel_means(real, fake, n, sm, mr, mf);
+    float ca = 0.f, cb = 0.f;  // counts: exact in fp32 (n < 2^24 checked by the host)
+    for (long i = threadIdx.x; i < n; i += LT) {
+        ca += 1.f + (real[i] - mf) > 0.f ? 1.f : 0.f;
+        cb += 1.f - (fake[i] - mr) > 0.f ? 1.f : 0.f;
+    }
+    const float ma = block_sum_all(ca, sm) / (float)n, mb = block_sum_all(cb, sm) / (float)n;
+    const float g = gout[0] / (float)n;
+    for (long i = threadIdx.x; i < n; i += LT) {
+        if (greal) greal[i] = g * ((1.f + (real[i] - mf) > 0.f ? 1.f : 0.f) + mb);
+        if (gfake) gfake[i] = -g * ((1.f - (fake[i] - mr) > 0.f ? 1.f : 0.f) + ma);
+    }
+}
+
+// ---- mean of the k smallest of n <= TOPK_MAX values (top_k_training): ONE block, ranks by counting ---------------------
+// rank_i = #{j : v_j < v_i, or v_j == v_i and j < i}; element i is selected when rank_i < k, so among equal values the
+// lower index wins (torch.topk leaves that choice open; the mean is the same).  The backward writes g / k at the selected
+// positions and 0 elsewhere.
+constexpr int TOPK_MAX = 1024;
+
+__device__ __forceinline__ bool topk_selected(const float* sv, int n, int k, int i) {
+    const float vi = sv[i];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+        const float vj = sv[j];
+        rank += (vj < vi || (vj == vi && j < i)) ? 1 : 0;
+    }
+    return rank < k;
+}
+
+__global__ __launch_bounds__(LT) void topk_mean_fwd_kernel(const float* v, float* out, int n, int k) {
+    __shared__ float sv[TOPK_MAX];
+    __shared__ float sm[LT / 64];
+    for (int i = threadIdx.x; i < n; i += LT) sv[i] = v[i];
+    __syncthreads();
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += LT)
+        if (topk_selected(sv, n, k, i)) s += sv[i];
+    s = block_sum_all(s, sm);
+    if (threadIdx.x == 0) out[0] = s / (float)k;
+}
+
+__global__ __launch_bounds__(LT) void topk_mean_bwd_kernel(const float* v, const float* gout, float* gv, int n, int k) {
+    __shared__ float sv[TOPK_MAX];
+    for (int i = threadIdx.x; i < n; i += LT) sv[i] = v[i];
+    __syncthreads();
+    const float g = __fdiv_rn(gout[0], (float)k);  // the correctly rounded quotient, whatever the build's division flags
+    for (int i = threadIdx.x; i < n; i += LT) gv[i] = topk_selected(sv, n, k, i) ? g : 0.f;
 }
 
 // ---- path lengths: one block per sample ------------------------------------------------------------------------------
@@ -245,6 +338,38 @@ int stylex_hinge_bwd(const float* real, const float* fake, const float* gout, fl
     if (!fake || !gout || n < 1 || (mode != 0 && mode != 1) || (mode == 0 && !real) || (!greal && !gfake)) return STYLEX_EINVAL;
     stylex_note_kernel("hinge_bwd_kernel");
     hipLaunchKernelGGL(hinge_bwd_kernel, dim3((unsigned)((n + LT - 1) / LT)), dim3(LT), 0, (hipStream_t)stream, real, fake, gout, greal, gfake, (long)n, mode);
+    return (int)hipGetLastError();
+}
+
+// relativistic average hinge of n logits per side (n < 2^24: the backward counts in fp32)
+int stylex_hinge_rel_fwd(const float* real, const float* fake, float* out, int64_t n, void* stream) {
+    if (!real || !fake || !out || n < 1 || n >= (1 << 24)) return STYLEX_EINVAL;
+    stylex_note_kernel("hinge_rel_fwd_kernel");
+    hipLaunchKernelGGL(hinge_rel_fwd_kernel, dim3(1), dim3(LT), 0, (hipStream_t)stream, real, fake, out, (long)n);
+    return (int)hipGetLastError();
+}
+
+int stylex_hinge_rel_bwd(const float* real, const float* fake, const float* gout, float* greal, float* gfake, int64_t n, void* stream) {
+    if (!real || !fake || !gout || (!greal && !gfake) || n < 1 || n >= (1 << 24)) return STYLEX_EINVAL;
+    stylex_note_kernel("hinge_rel_bwd_kernel");
+    hipLaunchKernelGGL(hinge_rel_bwd_kernel, dim3(1), dim3(LT), 0, (hipStream_t)stream, real, fake, gout, greal, gfake, (long)n);
+    return (int)hipGetLastError();
+}
+
+int64_t stylex_topk_mean_max_n(void) { return TOPK_MAX; }
+
+// mean of the k smallest of v[0..n), 1 <= k <= n <= stylex_topk_mean_max_n(); ties go to the lower index
+int stylex_topk_mean_fwd(const float* v, float* out, int64_t n, int64_t k, void* stream) {
+    if (!v || !out || n < 1 || n > TOPK_MAX || k < 1 || k > n) return STYLEX_EINVAL;
+    stylex_note_kernel("topk_mean_fwd_kernel");
+    hipLaunchKernelGGL(topk_mean_fwd_kernel, dim3(1), dim3(LT), 0, (hipStream_t)stream, v, out, (int)n, (int)k);
+    return (int)hipGetLastError();
+}
+
+int stylex_topk_mean_bwd(const float* v, const float* gout, float* gv, int64_t n, int64_t k, void* stream) {
+    if (!v || !gout || !gv || n < 1 || n > TOPK_MAX || k < 1 || k > n) return STYLEX_EINVAL;
+    stylex_note_kernel("topk_mean_bwd_kernel");
+    hipLaunchKernelGGL(topk_mean_bwd_kernel, dim3(1), dim3(LT), 0, (hipStream_t)stream, v, gout, gv, (int)n, (int)k);
     return (int)hipGetLastError();
 }
 

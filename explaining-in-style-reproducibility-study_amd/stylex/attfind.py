@@ -31,7 +31,9 @@ def styles_def_to_tensor(styles_def):
 
 def _prefix_states(G, w_tensor, noise):
     """Feature map / RGB entering every block for one image (batch 1), plus the unperturbed block styles."""
-    x = G.initial_conv(G.initial_block.expand(1, -1, -1, -1))
+    # no_const: the first activation comes from the image's own w; a perturbed style BIAS does not enter it, so the
+    # prefix states stay valid for every perturbation
+    x = G.initial_conv(G.first_activation(w_tensor))
     rgb, states = None, []
     for li, block in enumerate(G.blocks):
         istyle = w_tensor[:, li]
@@ -216,7 +218,7 @@ def change_images(G, classifier, dlatents, sindex, style_direction_index, s_styl
     base_img, coords = G(styles_def_to_tensor([(w, G.num_layers)]), noise, get_style_coords=True)
     target = float(s_style_min) if style_direction_index == 0 else float(s_style_max)
     delta = (target - coords[:, int(sindex)]) * shift_size
-    x = G.initial_conv(G.initial_block.expand(n, -1, -1, -1))
+    x = G.initial_conv(G.first_activation(styles_def_to_tensor([(w, G.num_layers)])))
     rgb = None
     for li, block in enumerate(G.blocks):
         styles = None

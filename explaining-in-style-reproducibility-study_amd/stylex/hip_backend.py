@@ -151,6 +151,11 @@ SIGNATURES = {
     "stylex_adam_pack_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_hinge_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "stylex_hinge_bwd": (ctypes.c_int, [_c_f] * 5 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_hinge_rel_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_void_p]),
+    "stylex_hinge_rel_bwd": (ctypes.c_int, [_c_f] * 5 + [ctypes.c_int64, ctypes.c_void_p]),
+    "stylex_topk_mean_max_n": (ctypes.c_int64, []),
+    "stylex_topk_mean_fwd": (ctypes.c_int, [_c_f, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "stylex_topk_mean_bwd": (ctypes.c_int, [_c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_pl_lengths_fwd": (ctypes.c_int, [_c_f, _c_f, _i64p, ctypes.c_void_p]),
     "stylex_pl_lengths_bwd": (ctypes.c_int, [_c_f] * 4 + [_i64p, ctypes.c_void_p]),
     "stylex_kl_logits_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_void_p]),
@@ -170,6 +175,10 @@ SIGNATURES = {
     "stylex_dwconv3x3_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_void_p]),
     "stylex_dwconv3x3_wgrad_blocks": (ctypes.c_int, [_i64p]),
     "stylex_dwconv3x3_bwd_weight": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_initial_block_supported": (ctypes.c_int, [_i64p]),
+    "stylex_initial_block_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_initial_block_bwd_data": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_initial_block_bwd_weight": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_void_p]),
     "stylex_resample_rows_u8": (ctypes.c_int, [ctypes.c_void_p, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_f,
                                                ctypes.c_int64, _c_f, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_resample_cols_u8": (ctypes.c_int, [ctypes.c_void_p, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_f,
@@ -445,7 +454,9 @@ def _adam_dtype():
     return _ADAM_DT
 
 
-_ADAM_KIND_CODE = {"pack": 0, "s2d": 1, "bf16mat": 0, "wsq": 2}  # stylex_adam_tensor.var[].kind; other kinds stay lazy
+# stylex_adam_tensor.var[].kind; other kinds stay lazy.  "initw" (the bf16 [D][16 C] copy of the no_const transposed-conv
+# weight) is the forward pack of a T = 1 conv over the weight read as a [D][16 C] matrix, like "bf16mat"
+_ADAM_KIND_CODE = {"pack": 0, "s2d": 1, "bf16mat": 0, "wsq": 2, "initw": 0}
 
 
 def _adam_copies_of(p):
@@ -536,8 +547,8 @@ def adam_pack_step(opt):
             shape = tuple(p.shape)
             if len(shape) == 4 and shape[2] * shape[3] <= 9:
                 n, c, t = shape[0], shape[1], shape[2] * shape[3]
-            elif copies and len(shape) == 2:
-                n, c, t = shape[0], shape[1], 1
+            elif copies and (len(shape) == 2 or all(e.kind == "initw" for e, *_ in copies)):
+                n, c, t = shape[0], p.numel() // shape[0], 1  # a matrix (or a weight every copy of which reads it as one)
             else:
                 n, c, t = 0, 0, 0
                 copies = []
@@ -1400,6 +1411,49 @@ def hinge_bwd(real, fake, gout, want_real, want_fake, mode=0):
     return greal, gfake
 
 
+def hinge_rel_fwd(real, fake):
+    """Relativistic average hinge: mean(relu(1 + real - mean(fake)) + relu(1 - fake + mean(real))), one launch."""
+    lib = _ensure_device(fake)
+    out = _empty((), dtype=torch.float32, device=fake.device)
+    _check(lib.stylex_hinge_rel_fwd(_ptr(real), _ptr(fake), _ptr(out), fake.numel(), _stream()), "stylex_hinge_rel_fwd")
+    return out
+
+
+def hinge_rel_bwd(real, fake, gout, want_real, want_fake):
+    lib = _ensure_device(fake)
+    greal = torch.empty_like(real) if want_real else None
+    gfake = torch.empty_like(fake) if want_fake else None
+    _check(lib.stylex_hinge_rel_bwd(_ptr(real), _ptr(fake), _ptr(gout), _ptr(greal), _ptr(gfake), fake.numel(), _stream()),
+           "stylex_hinge_rel_bwd")
+    return greal, gfake
+
+
+_TOPK_MAX = None
+
+
+def topk_mean_max_n():
+    """Largest n of the one-block selection kernel (a larger slice takes torch.topk)."""
+    global _TOPK_MAX
+    if _TOPK_MAX is None:
+        _TOPK_MAX = int(load_library().stylex_topk_mean_max_n())
+    return _TOPK_MAX
+
+
+def topk_mean_fwd(v, k):
+    """Mean of the k smallest of the fp32 vector v; among equal values the lower index is taken."""
+    lib = _ensure_device(v)
+    out = _empty((), dtype=torch.float32, device=v.device)
+    _check(lib.stylex_topk_mean_fwd(_ptr(v), _ptr(out), v.numel(), int(k), _stream()), "stylex_topk_mean_fwd")
+    return out
+
+
+def topk_mean_bwd(v, gout, k):
+    lib = _ensure_device(v)
+    gv = torch.empty_like(v)
+    _check(lib.stylex_topk_mean_bwd(_ptr(v), _ptr(gout), _ptr(gv), v.numel(), int(k), _stream()), "stylex_topk_mean_bwd")
+    return gv
+
+
 def pl_lengths_fwd(g):
     lib = _ensure_device(g)
     out = _empty(g.shape[0], dtype=torch.float32, device=g.device)
@@ -1670,6 +1724,65 @@ def _pow2_lanes(c):
 
 def chan_norm_supported(c):
     return _pow2_lanes(c)
+
+
+# ---- no_const: the generator's first activation from the styles (csrc/initial_block.hip) ----------------------------------
+
+def initial_block_supported(b, l, d, c):
+    """Shapes the three initial-block launches cover; anything else stays on the composable (ATen) formula."""
+    return bool(load_library().stylex_initial_block_supported(_shape(b, l, d, c)))
+
+
+def _initial_block_operand(w, precision):
+    """(weight operand, dtype code) of the initial-block kernels: the fp32 weight itself in the fp32 mode and for any
+    tensor that is not a Parameter (the second-order passes hand a gradient in); in the bf16 modes the cached bf16 copy
+    [D][16 C] of the Parameter (operand_cache kind "initw"; the fused Adam launch rewrites it in place)."""
+    if precision == F32 or not (isinstance(w, torch.nn.Parameter) and _packable(w)):
+        return _f32c(w.detach()), 0
+    pack = packs.get((w,), "initw", lambda: (w.detach().reshape(w.shape[0], -1).to(torch.bfloat16).contiguous(),),
+                     recipe=lambda p: _initial_block_operand(p, precision))[0]
+    return pack, 1
+
+
+def _initial_block_dims(styles, w):
+    b, l, d = styles.shape
+    assert w.dim() == 4 and w.shape[0] == d and tuple(w.shape[2:]) == (4, 4), (tuple(styles.shape), tuple(w.shape))
+    return b, l, d, w.shape[1]
+
+
+def initial_block_fwd(styles, w, precision, out_dtype):
+    """x [B, C, 4, 4] (channels-last, out_dtype) = conv_transpose2d(styles.mean(1)[:, :, None, None], w); styles fp32 [B, L, D]."""
+    lib = _ensure_device(styles)
+    b, l, d, c = _initial_block_dims(styles, w)
+    wop, wdt = _initial_block_operand(w, precision)
+    x = _empty((b, c, 4, 4), dtype=out_dtype, device=styles.device, memory_format=torch.channels_last)
+    _check(lib.stylex_initial_block_fwd(_ptr(styles), _ptr(wop), _ptr(x), _shape(b, l, d, c), wdt, _adt(x), _stream()),
+           "stylex_initial_block_fwd")
+    return x
+
+
+def initial_block_bwd_data(gx, w, l, precision):
+    """dstyles fp32 [B, L, D]: (1 / L) * sum over (c, i, j) of gx * w, the same row for every l."""
+    lib = _ensure_device(gx)
+    assert is_cl(gx) and tuple(gx.shape[2:]) == (4, 4) and gx.shape[1] == w.shape[1]
+    b, c, d = gx.shape[0], gx.shape[1], w.shape[0]
+    wop, wdt = _initial_block_operand(w, precision)
+    ds = _empty((b, l, d), dtype=torch.float32, device=gx.device)
+    _check(lib.stylex_initial_block_bwd_data(_ptr(gx), _ptr(wop), _ptr(ds), _shape(b, l, d, c), wdt, _adt(gx), _stream()),
+           "stylex_initial_block_bwd_data")
+    return ds
+
+
+def initial_block_bwd_weight(styles, gx):
+    """dw fp32 [D, C, 4, 4] = sum_b styles[b].mean(0)[d] * gx[b, c, i, j]."""
+    lib = _ensure_device(gx)
+    assert is_cl(gx) and tuple(gx.shape[2:]) == (4, 4) and gx.shape[0] == styles.shape[0]
+    b, l, d = styles.shape
+    c = gx.shape[1]
+    dw = _empty((d, c, 4, 4), dtype=torch.float32, device=gx.device)
+    _check(lib.stylex_initial_block_bwd_weight(_ptr(styles), _ptr(gx), _ptr(dw), _shape(b, l, d, c), _adt(gx), _stream()),
+           "stylex_initial_block_bwd_weight")
+    return dw
 
 
 def dwconv3x3_supported(c):

@@ -363,12 +363,14 @@ class Generator(nn.Module):  # reference :747-825
     def __init__(self, image_size, latent_dim, network_capacity=16, transparent=False, attn_layers=[], no_const=False,
                  fmap_max=512):
         super().__init__()
-        assert not no_const, "the no_const variant is out of scope (SURVEY §2a)"
         self.image_size, self.latent_dim = image_size, latent_dim
         self.num_layers = int(log2(image_size) - 1)
         filters = generator_filters(image_size, network_capacity, fmap_max)
         self.no_const = no_const
-        self.initial_block = nn.Parameter(torch.randn((1, filters[0], 4, 4)))
+        if no_const:  # reference :766-767; a plain ConvTranspose2d: _init_weights leaves its default init alone
+            self.to_initial_block = nn.ConvTranspose2d(latent_dim, filters[0], 4, 1, 0, bias=False)
+        else:
+            self.initial_block = nn.Parameter(torch.randn((1, filters[0], 4, 4)))
         self.initial_conv = HipConv2d(filters[0], filters[0], 3, padding=1)
         self.blocks = nn.ModuleList([])
         self.attns = nn.ModuleList([])
@@ -378,9 +380,15 @@ class Generator(nn.Module):  # reference :747-825
             self.blocks.append(GeneratorBlock(latent_dim, filters[ind], filters[ind + 1], upsample=ind != 0,
                                               upsample_rgb=ind != self.num_layers - 1, rgba=transparent))
 
+    def first_activation(self, styles):
+        """The 4x4 input of initial_conv for styles [B, L, D]: the learned constant, or with no_const the transposed conv
+        of the layer-averaged style (reference :798-802)."""
+        if self.no_const:
+            return ops.initial_block(styles, self.to_initial_block.weight)
+        return self.initial_block.expand(styles.shape[0], -1, -1, -1)
+
     def forward(self, styles, input_noise, get_style_coords=False):
-        batch = styles.shape[0]
-        x = self.initial_conv(self.initial_block.expand(batch, -1, -1, -1))
+        x = self.initial_conv(self.first_activation(styles))
         rgb, coords = None, []
         # The toRGB chain runs on the caller's stream.  (Rounds 1-5 kept an opt-in variant that ran it one block behind on a
         # side HIP stream — +0.8 % — which produced run-to-run differences: deleted in round 6.  Their very likely cause was

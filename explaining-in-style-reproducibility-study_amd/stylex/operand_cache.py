@@ -1,5 +1,5 @@
 """Cache of parameter-derived operand copies: packed conv weights, GEMM matrices, tap sums of squares, scaled linear
-parameters, bias vectors.  The one place that knows what an entry holds and when it may be served (torch only: CPU ranks
+parameters, bias vectors, the bf16 copy of the no_const transposed-conv weight (`initw`).  The one place that knows what an entry holds and when it may be served (torch only: CPU ranks
 import it for `mark_updated` without loading the kernel library).
 
 An entry is served only while every owner is the same live object, at the same address (`p.data = other` and
@@ -14,7 +14,7 @@ ON = os.environ.get("STYLEX_PACK_CACHE", "1") != "0"  # probe switch: 0 = repack
 # built from, and a hit whose parameters no longer have that checksum raises — the failure mode of round 3's
 # stale-operand bug (an update path that bumps neither Parameter._version nor the `mark_updated` stamp).
 CHECK = os.environ.get("STYLEX_CACHE_CHECK", "0") == "1"
-KINDS = ("pack", "s2d", "bf16mat", "wsq", "padc", "fwd_as_dgrad", "eql", "vec")
+KINDS = ("pack", "s2d", "bf16mat", "wsq", "padc", "fwd_as_dgrad", "eql", "vec", "initw")
 
 
 def stream_id():

@@ -345,6 +345,39 @@ class _Hinge(torch.autograd.Function):
         return greal, gfake, None
 
 
+class _HingeRel(torch.autograd.Function):
+    """rel_disc_loss (reference :1338-1342): the hinge of real - mean(fake) and fake - mean(real); both means carry gradient."""
+
+    @staticmethod
+    def forward(ctx, real, fake):
+        real, fake = hb._f32c(real), hb._f32c(fake)
+        ctx.save_for_backward(real, fake)
+        return hb.hinge_rel_fwd(real, fake)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        real, fake = ctx.saved_tensors
+        return hb.hinge_rel_bwd(real, fake, hb._f32c(g), ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+
+
+class _TopKMean(torch.autograd.Function):
+    """top_k_training (reference :1401-1407): mean of the k smallest values; among equal values the lower index is taken."""
+
+    @staticmethod
+    def forward(ctx, v, k):
+        v = hb._f32c(v)
+        ctx.save_for_backward(v)
+        ctx.k = k
+        return hb.topk_mean_fwd(v, k)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (v,) = ctx.saved_tensors
+        return hb.topk_mean_bwd(v, hb._f32c(g), ctx.k), None
+
+
 class _PLLengths(torch.autograd.Function):
     """sqrt(mean_l(sum_d g^2)) per sample (reference calc_pl_lengths :316)."""
 
@@ -395,13 +428,24 @@ class _L1Mean(torch.autograd.Function):
         return ga, gb, None
 
 
-def hinge_loss(real, fake):
-    if _loss_fusable(real, fake) and real.shape == fake.shape:
+def hinge_loss(real, fake, relativistic=False):
+    """relativistic (rel_disc_loss, reference :1338-1342): each side is taken relative to the mean of the other."""
+    if relativistic:
+        if _loss_fusable(real, fake) and real.shape == fake.shape and real.numel() < (1 << 24):
+            return _HingeRel.apply(real, fake)
+        real, fake = real - fake.mean(), fake - real.mean()
+    elif _loss_fusable(real, fake) and real.shape == fake.shape:
         return _Hinge.apply(real, fake, 0)
     return (F.relu(1 + real) + F.relu(1 - fake)).mean()
 
 
-def gen_hinge_loss(fake):
+def gen_hinge_loss(fake, k=None):
+    """k (top_k_training, reference :1401-1407): the mean of the k smallest logits instead of all of them.  Which of
+    several EQUAL logits count is left open by torch.topk; the fused kernel takes the lower index (same loss value)."""
+    if k is not None and k != fake.numel():
+        if _loss_fusable(fake) and fake.dim() == 1 and fake.numel() <= hb.topk_mean_max_n():
+            return _TopKMean.apply(fake, int(k))
+        return fake.topk(k=int(k), largest=False)[0].mean()
     if _loss_fusable(fake):
         return _Hinge.apply(None, fake, 1)
     return fake.mean()
@@ -1545,3 +1589,87 @@ def linear_attention_core(q, k, v, heads):
     if _attn_fused(q) and hb.linattn_supported(q.shape[1], heads):
         return _LinAttnFused.apply(_act(q), _act(k), _act(v), int(heads))
     return _narrow(_linattn_composable(q, k, v, heads), q)
+
+
+# ------------------------------------------------------------------------------------------
+# no_const (reference stylex/stylex_train.py:766-769, :798-802): the generator's first activation is a transposed conv of
+# the layer-averaged style instead of a learned constant.  On its 1x1 input that is x = mean_l(styles) @ W, bilinear in
+# (styles, W), and like the dense conv triad it is closed under differentiation (csrc/initial_block.hip):
+#
+#     IB(s, w)    --bwd-->  IBD(gx, w), IBW(s, gx)
+#     IBD(gx, w)  --bwd-->  IB(ggs, w), IBW(ggs, gx)
+#     IBW(s, gx)  --bwd-->  IBD(gx, ggw), IB(s, ggw)
+#
+# so the path-length step (styles -> x -> image differentiated twice) stays on the three launches.  CPU tensors and shapes
+# the kernels do not cover take the reference's formula in plain torch ops; like the attention ops this one does not go
+# through the implementation object.
+# ------------------------------------------------------------------------------------------
+
+_INITIAL_BLOCK_FUSED = os.environ.get("STYLEX_INITIAL_BLOCK_FUSED", "1") != "0"
+
+
+def set_initial_block_fused(flag):
+    """False: CUDA tensors take the composable (ATen) path too — the baseline of an A/B."""
+    global _INITIAL_BLOCK_FUSED
+    prev = _INITIAL_BLOCK_FUSED
+    _INITIAL_BLOCK_FUSED = bool(flag)
+    return prev
+
+
+def _initial_block_composable(styles, w):
+    return F.conv_transpose2d(_wide(styles).mean(dim=1)[:, :, None, None], w)
+
+
+class _InitialBlock(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, styles, w, out_dtype):
+        styles = hb._f32c(styles)
+        ctx.save_for_backward(styles, w)
+        return hb.initial_block_fwd(styles, w, _PRECISION, out_dtype)
+
+    @staticmethod
+    def backward(ctx, gx):
+        styles, w = ctx.saved_tensors
+        ds = _InitialBlockDgrad.apply(gx, w, styles.shape[1]) if ctx.needs_input_grad[0] else None
+        dw = _InitialBlockWgrad.apply(styles, gx) if _want_param_grad(ctx, 1) else None
+        return ds, dw, None
+
+
+class _InitialBlockDgrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gx, w, layers):
+        gx = hb.to_cl(gx)
+        ctx.save_for_backward(gx, w)
+        return hb.initial_block_bwd_data(gx, w, layers, _PRECISION)
+
+    @staticmethod
+    def backward(ctx, ggs):
+        gx, w = ctx.saved_tensors
+        d_gx = _InitialBlock.apply(ggs, w, gx.dtype) if ctx.needs_input_grad[0] else None
+        d_w = _InitialBlockWgrad.apply(ggs, gx) if _want_param_grad(ctx, 1) else None
+        return d_gx, d_w, None
+
+
+class _InitialBlockWgrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, styles, gx):
+        styles, gx = hb._f32c(styles), hb.to_cl(gx)
+        ctx.save_for_backward(styles, gx)
+        return hb.initial_block_bwd_weight(styles, gx)
+
+    @staticmethod
+    def backward(ctx, ggw):
+        styles, gx = ctx.saved_tensors
+        d_s = _InitialBlockDgrad.apply(gx, ggw, styles.shape[1]) if ctx.needs_input_grad[0] else None
+        d_gx = _InitialBlock.apply(styles, ggw, gx.dtype) if ctx.needs_input_grad[1] else None
+        return d_s, d_gx
+
+
+def initial_block(styles, weight):
+    """ConvTranspose2d(D, C, 4, 1, 0, bias=False)(styles.mean(dim=1)[:, :, None, None]); styles [B, L, D], weight
+    [D, C, 4, 4].  On the GPU the result is channels-last in the activation dtype."""
+    if (styles.is_cuda and _INITIAL_BLOCK_FUSED and styles.dim() == 3 and weight.dim() == 4 and tuple(weight.shape[2:]) == (4, 4)
+            and weight.shape[0] == styles.shape[2] and weight.dtype == torch.float32
+            and hb.initial_block_supported(*styles.shape, weight.shape[1])):
+        return _InitialBlock.apply(styles, weight, act_dtype())
+    return _narrow(_initial_block_composable(styles, weight), styles)

@@ -324,12 +324,12 @@ def calc_pl_lengths(styles, images, pl_noise=None):
 
 # The scalar reductions below are one forward and one backward launch each on the GPU (csrc/losses.hip,
 # ops._Hinge / _KLLogits / _L1Mean / _PLLengths); on other devices the reference's torch composition.
-def gen_hinge_loss(fake, real):
-    return ops.gen_hinge_loss(fake)  # fake.mean()
+def gen_hinge_loss(fake, real, k=None):
+    return ops.gen_hinge_loss(fake, k)  # fake.mean(); k: the mean of the k smallest (top_k_training)
 
 
-def hinge_loss(real, fake):
-    return ops.hinge_loss(real, fake)  # (F.relu(1 + real) + F.relu(1 - fake)).mean()
+def hinge_loss(real, fake, relativistic=False):
+    return ops.hinge_loss(real, fake, relativistic)  # (F.relu(1 + real) + F.relu(1 - fake)).mean()
 
 
 def lpips_normalize(images):
@@ -650,7 +650,18 @@ class Trainer:
         self.config_path = self.models_dir / name / ".config.json"
         assert log2(image_size).is_integer(), "image size must be a power of 2 (64, 128, 256, 512, 1024)"
         assert not fp16, "apex fp16 is out of scope; use ops.set_precision('bf16')"
-        assert not (dual_contrast_loss or top_k_training or rel_disc_loss or cl_reg), "variant losses are out of scope"
+        # Checked against the reference itself (tools/make_golden_variants.py, tests/golden/steps_rel_disc.npz): with
+        # dual_contrast_loss=True its generator phase unpacks `real_output, _ = D_aug(image_batch, ...)` from a [B] tensor
+        # (stylex_train.py:1398) and the first train() call raises.  There is no behaviour to match.
+        if dual_contrast_loss:
+            raise RuntimeError("dual_contrast_loss=True cannot run in the reference either: stylex_train.py:1398 unpacks "
+                               "`real_output, _ = D_aug(...)` from the discriminator's [B] output and the first train() call "
+                               "raises \"ValueError: too many values to unpack (expected 2)\"")
+        assert not cl_reg, "cl_reg needs the contrastive_learner package (no oracle to check against): out of scope"
+        assert not fq_layers, "fq_layers needs the vector_quantize_pytorch package (no oracle to check against): out of scope"
+        self.rel_disc_loss = bool(rel_disc_loss)
+        self.top_k_training = bool(top_k_training)
+        self.generator_top_k_gamma, self.generator_top_k_frac = generator_top_k_gamma, generator_top_k_frac
         self.image_size, self.network_capacity, self.fmap_max = image_size, network_capacity, fmap_max
         self.transparent = transparent
         self.fq_layers, self.fq_dict_size = cast_list(fq_layers), fq_dict_size
@@ -1069,7 +1080,7 @@ class Trainer:
         for r in reals:
             sl = slice(lo, lo + r.shape[0])
             lo += r.shape[0]
-            divergence = hinge_loss(real_out[sl], fake_out[sl])
+            divergence = hinge_loss(real_out[sl], fake_out[sl], self.rel_disc_loss)  # the means are per micro-step
             disc_loss = disc_loss + divergence
             if apply_gp:
                 gp = 10 * ((grad_norms[sl] - 1) ** 2).mean()
@@ -1134,9 +1145,10 @@ class Trainer:
         outs = self._fork(branches)
         fake_all = outs[0]
         total_all = 0
+        top_k = self._generator_top_k()
         for sl, enc, at in zip(spans, encs, where):
             generated = generated_all[sl]
-            loss = gen_hinge_loss(fake_all[sl], None)
+            loss = gen_hinge_loss(fake_all[sl], None, top_k)
             total = loss
             if apply_pl:
                 pl_lengths = pl_all[sl] if pl_all is not None else calc_pl_lengths(w_all, generated)
@@ -1192,6 +1204,25 @@ class Trainer:
         if s % self.save_every == 0 or s % self.evaluate_every == 0 or (s % 100 == 0 and s < 2500):
             return True
         return exists(self.calculate_fid_every) and s % self.calculate_fid_every == 0 and s != 0
+
+    def _generator_top_k(self):
+        """top_k_training (reference :1401-1407): how many of a micro-step's D(fake) logits the generator's adversarial loss
+        averages — the k smallest; None = all of them.  The reference's own expression on the same variables."""
+        if not self.top_k_training:
+            return None
+        batch_size = math.ceil(self.batch_size / self.world_size)
+        epochs = (self.steps * batch_size * self.gradient_accumulate_every) / len(self.dataset)
+        k_frac = max(self.generator_top_k_gamma ** epochs, self.generator_top_k_frac)
+        k = math.ceil(batch_size * k_frac)
+        if k == batch_size:
+            return None
+        if self.new_architecture:
+            # tools/make_golden_variants.py, tests/golden/steps_newarch_variants.npz (`top_k_error`): nothing to match
+            raise RuntimeError("top_k_training with k < batch_size cannot run in the reference's second architecture either: "
+                               "stylex_train_new.py:1472 keeps the (values, indices) pair of topk and gen_hinge_loss raises "
+                               "\"AttributeError: 'torch.return_types.topk' object has no attribute 'mean'\" "
+                               "(k = %d of %d at step %d)" % (k, batch_size, self.steps))
+        return k
 
     def _new_acc(self):
         acc = {k: torch.zeros((), device=self.device) for k in ("d", "g", "rec", "kl")}
@@ -1358,8 +1389,8 @@ class Trainer:
         is ~1100 kernel launches issued through ctypes/ATen (~70 ms of host time per step); captured once
         per step shape (with / without the gradient penalty) it replays with one hipGraphLaunch.
         Refused with attn_layers: the attention blocks have not been captured or checked under replay, the step then
-        runs eagerly."""
-        return self.graphs and self.device.type == "cuda" and not self.attn_layers
+        runs eagerly.  Refused with top_k_training: k changes from call to call and is baked into the launches."""
+        return self.graphs and self.device.type == "cuda" and not self.attn_layers and not self.top_k_training
 
     def _opt_step(self, opt):
         """Optimiser step + invalidation of the cached operand copies of the weights it changed (bf16 GEMM layouts,

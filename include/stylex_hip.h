@@ -480,6 +480,16 @@ int stylex_adam_pack_step(const stylex_adam_tensor* descs_dev, const int32_t* bl
 int stylex_hinge_fwd(const float* real, const float* fake, float* out, int64_t n, int mode, void* stream);
 int stylex_hinge_bwd(const float* real, const float* fake, const float* gout, float* greal, float* gfake, int64_t n, int mode,
                      void* stream);
+/* rel_disc_loss (:1338-1342): out = mean(relu(1 + real - mean(fake)) + relu(1 - fake + mean(real))), one block; the
+ * gradient flows through both means.  n < 2^24. */
+int stylex_hinge_rel_fwd(const float* real, const float* fake, float* out, int64_t n, void* stream);
+int stylex_hinge_rel_bwd(const float* real, const float* fake, const float* gout, float* greal, float* gfake, int64_t n,
+                         void* stream);
+/* top_k_training (:1401-1407): out = mean of the k smallest of v[0..n), 1 <= k <= n <= stylex_topk_mean_max_n(); ranks by
+ * counting in one block, equal values: the lower index is taken.  bwd: gv = gout / k at the selected positions, else 0. */
+int64_t stylex_topk_mean_max_n(void);
+int stylex_topk_mean_fwd(const float* v, float* out, int64_t n, int64_t k, void* stream);
+int stylex_topk_mean_bwd(const float* v, const float* gout, float* gv, int64_t n, int64_t k, void* stream);
 int stylex_pl_lengths_fwd(const float* g, float* len, const int64_t* shape, void* stream);
 int stylex_pl_lengths_bwd(const float* g, const float* len, const float* glen, float* gg, const int64_t* shape, void* stream);
 int stylex_kl_logits_fwd(const float* real, const float* fake, float* out, const int64_t* shape, void* stream);
@@ -555,6 +565,19 @@ int stylex_resample_cols_u8(const int32_t* table_host, const int32_t* table_dev,
                             float* out, int64_t out_floats, void* stream);
 int stylex_crop_lut_u8(const int32_t* table_host, const int32_t* table_dev, int64_t table_ints, int64_t first_job, int64_t njobs,
                        const void* src, int64_t src_bytes, const float* lut, float* out, int64_t out_floats, void* stream);
+
+/* no_const (stylex_train.py:766-769, :798-802): x = ConvTranspose2d(D, C, 4, 1, 0, bias=False)(styles.mean(1)[:, :, None, None]).
+ * shape = {B, L, D, C}; styles / dstyles fp32 [B][L][D]; w [D][C][4][4] fp32 (w_dtype 0) or a bf16 copy in the same
+ * order (1); x / gx channels-last [B][4][4][C], fp32 or bf16 (act_dtype); dw fp32 [D][C][4][4].  The mean over L is taken
+ * while the styles are read; the data gradient writes the same row for every l.  Deterministic (no atomics).
+ * stylex_initial_block_supported: 1 when the three launches cover the shape (B <= 65535, L <= 64, D <= 1024, C <= 512). */
+int stylex_initial_block_supported(const int64_t* shape);
+int stylex_initial_block_fwd(const float* styles, const void* w, void* x, const int64_t* shape, int w_dtype, int act_dtype,
+                             void* stream);
+int stylex_initial_block_bwd_data(const void* gx, const void* w, float* dstyles, const int64_t* shape, int w_dtype, int act_dtype,
+                                  void* stream);
+int stylex_initial_block_bwd_weight(const float* styles, const void* gx, float* dw, const int64_t* shape, int act_dtype,
+                                    void* stream);
 
 #ifdef __cplusplus
 }
