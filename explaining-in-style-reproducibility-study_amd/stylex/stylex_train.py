@@ -17,7 +17,9 @@ AttFind notebook imports.  New, MI355X-first behaviour:
     to wrap (:1188-1193).
 """
 import atexit
+import dataclasses
 import threading
+from collections import namedtuple
 import json
 import math
 import multiprocessing
@@ -190,18 +192,23 @@ class _Staging:
         # on the compute stream sits behind that backlog and then executes IN ORDER between two kernels (0.35-0.4 ms
         # per 8 MB noise plane, four per step, nothing else running); on its own stream the SDMA engine moves it while
         # the compute kernels ahead of it are still running, and the consumer only waits for the (long finished) event.
+        out, slot[1] = cls.copy_up(fill(slot[0]), device)
+        return out
+
+    @classmethod
+    def copy_up(cls, host, device):
+        """Copy `host` on the device's upload stream, make the current stream wait; returns (device tensor, event)."""
         cur = torch.cuda.current_stream(device)
         up = cls._upload_streams.get(device)
         if up is None:
             up = cls._upload_streams[device] = torch.cuda.Stream(device)
-        host = fill(slot[0])
         with torch.cuda.stream(up):
             out = host.to(device, non_blocking=True)
-            slot[1] = torch.cuda.Event()
-            slot[1].record(up)
-        cur.wait_event(slot[1])
+            done = torch.cuda.Event()
+            done.record(up)
+        cur.wait_event(done)
         out.record_stream(cur)
-        return out
+        return out, done
 
 
 def _release_staging_at_exit():
@@ -596,6 +603,30 @@ def _lazy_loss(name):
     return property(get, put)
 
 
+# One micro-step's inputs.  kind "enc": `batch` is encoded (and conditions: `cond` is the same tensor); "noise": `latents` =
+# [(z, n_layers), ...] as drawn by noise_list / mixed_list; "noise_static", the graph form: `latents` = (z1, z2, tt) in
+# static buffers, the layer split `tt` a device scalar.  `cond`: the batch whose classifier probabilities condition the
+# new architecture (None in the graph form, which that architecture never takes).
+_Micro = namedtuple("_Micro", "kind inoise batch latents cond", defaults=(None, None, None))
+# What one micro-step group of a phase reads: `reals` in the D phase, `pl_noises` in G's path-length steps.
+_PhaseInputs = namedtuple("_PhaseInputs", "micro reals pl_noises", defaults=((), ()))
+# The device->host copy of a step's scalars (Trainer._resolve_losses); `done`: its event, None on the CPU.
+_PendingLosses = namedtuple("_PendingLosses", "host done has_gp keep_rec")
+
+
+@dataclasses.dataclass
+class _DrawState:
+    """Alternating training within one train() call: does the next micro-step encode a batch, and the latent draw
+    (noise_list / mixed_list) the last noise micro-step of the discriminator phase chose."""
+    encoder_input: bool = False
+    latents_fn: object = None
+
+    def next_phase(self, alternating):
+        """Between the discriminator phase's draws and the generator phase's (reference :1371-1372)."""
+        if alternating:
+            self.encoder_input = False
+
+
 class Trainer:
     # Same attribute names as the reference (:1108-1116), backed by ONE asynchronous device->host copy per
     # step: train() does not wait for the GPU, so the host prepares the next step's inputs while the GPU
@@ -605,7 +636,8 @@ class Trainer:
     total_rec_loss = _lazy_loss("total_rec_loss")
     total_kl_loss = _lazy_loss("total_kl_loss")
     last_gp_loss = _lazy_loss("last_gp_loss")
-    _pending = None
+    _pending = None  # _PendingLosses of the last step until a scalar is read (class level: the properties above read it)
+
     def __init__(self, name="default", results_dir="results", models_dir="models", base_dir="./", image_size=128,
                  network_capacity=16, fmap_max=512, transparent=False, batch_size=4, mixed_prob=0.9,
                  gradient_accumulate_every=1, lr=2e-4, lr_mlp=0.1, ttur_mult=2, rel_disc_loss=False, num_workers=None,
@@ -709,6 +741,8 @@ class Trainer:
         self.graphs = (os.environ.get("STYLEX_GRAPHS", "0") == "1") if graphs is None else bool(graphs)
         self.graph_warmup = graph_warmup
         self._static, self._graph_cache, self._graph_pool, self._calls, self._graph_warm = {}, {}, None, 0, set()
+        # NaN found by a lazily read loss copy | _fork's branch streams (made at first use) | G-phase draw still running
+        self._nan, self._side_streams, self._g_fut = False, None, None
         # backward-time raise_if_nan hook (reference :1352): opt-in, and never under DDP — it would raise on ONE rank
         # from inside a backward whose bucket all-reduces the other ranks are already waiting in; there the MAX-reduced
         # device-side flag of train() is the (collective) NaN check
@@ -767,6 +801,10 @@ class Trainer:
     @property
     def checkpoint_num(self):
         return floor(self.steps // self.save_every)
+
+    _rank_batch = property(lambda self: math.ceil(self.batch_size / self.world_size))  # rows of a micro-step on this rank
+    # width of a drawn latent: the new architecture appends the class probabilities to W instead
+    _z_dim = property(lambda self: self.StylEx.G.latent_dim - (self.StylEx.num_classes if self.new_architecture else 0))
 
     @property
     def hparams(self):
@@ -835,7 +873,7 @@ class Trainer:
             sampler = DistributedSampler(ds, rank=self.rank, num_replicas=self.world_size,
                                          shuffle=True) if self.is_ddp else None
             self.loader, self.dataset = input_pipeline.make_device_loader(
-                ds, self.image_size, math.ceil(self.batch_size / self.world_size), self.device,
+                ds, self.image_size, self._rank_batch, self.device,
                 num_workers=num_workers, transparent=self.transparent, sampler=sampler, shuffle=not self.is_ddp,
                 generator=torch_rng)
         else:
@@ -843,7 +881,7 @@ class Trainer:
             sampler = DistributedSampler(self.dataset, rank=self.rank, num_replicas=self.world_size,
                                          shuffle=True) if self.is_ddp else None
             loader = data.DataLoader(self.dataset, num_workers=num_workers,
-                                     batch_size=math.ceil(self.batch_size / self.world_size), sampler=sampler,
+                                     batch_size=self._rank_batch, sampler=sampler,
                                      shuffle=not self.is_ddp, drop_last=True, pin_memory=torch.cuda.is_available())
             self.loader = cycle(loader)
         num_samples = len(self.dataset)
@@ -858,17 +896,7 @@ class Trainer:
         if batch.device == self.device or self.device.type != "cuda" or _capturing():
             return batch.to(self.device, non_blocking=True)
         # loader batches (pinned by the DataLoader) take the upload stream too, see _Staging.upload
-        cur = torch.cuda.current_stream(self.device)
-        up = _Staging._upload_streams.get(self.device)
-        if up is None:
-            up = _Staging._upload_streams[self.device] = torch.cuda.Stream(self.device)
-        with torch.cuda.stream(up):
-            out = batch.to(self.device, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(up)
-        cur.wait_event(ev)
-        out.record_stream(cur)
-        return out
+        return _Staging.copy_up(batch, self.device)[0]
 
     def _resolve_losses(self, raise_nan=True):
         """Wait for the pending loss copy of the last step (only that copy, not the stream) and publish the
@@ -876,17 +904,16 @@ class Trainer:
         calls this for the previous step once the next discriminator phase is enqueued, and before saving."""
         pend, self._pending = self._pending, None
         if pend is not None:
-            host, done, has_gp, keep_rec = pend
-            if done is not None:
-                done.synchronize()
-            vals = host.tolist()
+            if pend.done is not None:
+                pend.done.synchronize()
+            vals = pend.host.tolist()
             self.d_loss, self.g_loss = vals[0], vals[1]
-            if has_gp:
+            if pend.has_gp:
                 self.last_gp_loss = vals[4]
-            if keep_rec:
+            if pend.keep_rec:
                 self.total_rec_loss, self.total_kl_loss = vals[2], vals[3]
             self._nan = vals[5] > 0  # isnan(d_loss) | isnan(g_loss), OR-ed over the ranks under DDP
-        if raise_nan and getattr(self, "_nan", False):
+        if raise_nan and self._nan:
             self._nan = False
             print(f"NaN detected for generator or discriminator. Loading from checkpoint #{self.checkpoint_num}")
             self.load(self.checkpoint_num)
@@ -899,7 +926,7 @@ class Trainer:
         replays every node on its forward stream — backward.  Results are identical (no shared mutable state)."""
         if self.device.type != "cuda" or len(fns) < 2 or os.environ.get("STYLEX_STREAMS", "1") == "0":
             return [f() for f in fns]
-        if getattr(self, "_side_streams", None) is None:
+        if self._side_streams is None:
             self._side_streams = [torch.cuda.Stream(device=self.device) for _ in range(3)]
             # parameters shared by branches on different streams (encoder, classifier input) accumulate across
             # streams by design; the engine synchronises them — silence its advisory
@@ -937,17 +964,43 @@ class Trainer:
         w = styles_def_to_tensor([(torch.cat((enc, cond), dim=1), m.G.num_layers)])
         return enc, logits, w
 
-    def _styles_of(self, entry, probs=None):
-        """[B, L, latent] style tensor of a noise micro-step: ('noise', [(z, n_layers), ...], inoise) as drawn by
-        noise_list / mixed_list, or the graph form ('noise_static', (z1, z2, tt), inoise, None) whose layer split `tt` is a
-        device scalar, so that one captured graph serves every split (pure selection: identical values)."""
+    def _styles_of(self, e, probs=None):
+        """[B, L, latent] style tensor of a noise micro-step (see _Micro): the drawn form, or the graph form whose layer
+        split `tt` is a device scalar, so that one captured graph serves every split (pure selection: identical values —
+        but the style gradient sums in another order than the drawn form's expand, so the two forms stay apart)."""
         m = self.StylEx
-        if entry[0] == "noise":
-            return styles_def_to_tensor(latent_to_w(m.S, entry[1], probs))
-        z1, z2, tt = entry[1]
+        if e.kind == "noise":
+            return styles_def_to_tensor(latent_to_w(m.S, e.latents, probs))
+        z1, z2, tt = e.latents
         w1, w2 = m.S(z1), m.S(z2)
         first = torch.arange(m.G.num_layers, device=z1.device) < tt
         return torch.where(first[None, :, None], w1[:, None, :], w2[:, None, :])
+
+    def _micro_styles(self, micro):
+        """Both phases open with this: per micro-step the styles and, for an encoder one, (batch, encoder output, logits),
+        else None; and the group's conditioning probabilities (new architecture)."""
+        new = self.new_architecture
+        ws, encs, conds = [], [], []
+        for e in micro:
+            if e.kind == "enc":
+                enc_out, logits, w = self._styles_from_encoder(e.batch)
+                encs.append((e.batch, enc_out, logits))
+                p_i = F.softmax(logits, dim=1) if new else None
+            else:
+                # new architecture: the classifier runs on EVERY micro-step's conditioning batch (:1332-1333, :1437-1438)
+                p_i = F.softmax(self._classify(e.cond), dim=1) if new else None
+                w = self._styles_of(e, p_i)
+                encs.append(None)
+            ws.append(w)
+            conds.append(p_i)
+        return ws, encs, _cat(conds) if new else None
+
+    def _D_call(self, images, fuse, detach=False, probs=None):
+        m = self.StylEx
+        if fuse:  # AugWrapper at prob 0 is D itself; its random() draw is issued where the reference draws it
+            images = images.detach() if detach else images
+            return m.D(images, probabilities=probs) if self.new_architecture else m.D(images)
+        return m.D_aug(images, detach=detach, probabilities=probs, prob=self.aug_prob, types=self.aug_types)
 
     # -- host side of a phase: every RNG draw / loader fetch of its micro-steps, in the reference's order ---------
 
@@ -955,87 +1008,56 @@ class Trainer:
         """Discriminator-phase inputs of one micro-step group (:1299-1333): per micro-step the real batch, then either
         (encoder micro-step) a second loader batch + image noise, or (noise micro-step) random() for mixed_prob,
         [torch.rand(()) split], 1-2 latents, image noise; then the two AugWrapper draws."""
-        m = self.StylEx
-        batch_size = math.ceil(self.batch_size / self.world_size)
-        reals, micro = [], []
-        new = self.new_architecture
-        z_dim = m.G.latent_dim - (m.num_classes if new else 0)
+        m, new, batch_size = self.StylEx, self.new_architecture, self._rank_batch
+        reals, micro, size = [], [], m.G.image_size
         for _ in group:
             reals.append(self._next_batch())
             # new architecture: EVERY micro-step draws a conditioning batch (stylex_train_new.py:1329-1334); an
             # encoder micro-step encodes that same batch
             cond = self._next_batch() if new else None
-            if (not self.alternating_training) or st["encoder_input"]:
+            if (not self.alternating_training) or st.encoder_input:
                 batch2 = cond if new else self._next_batch()
-                micro.append(("enc", batch2, image_noise(batch_size, m.G.image_size, device=self.device), batch2))
-                st["encoder_input"] = False
+                micro.append(_Micro("enc", image_noise(batch_size, size, device=self.device), batch=batch2, cond=batch2))
+                st.encoder_input = False
             else:
-                st["latents_fn"] = mixed_list if random() < self.mixed_prob else noise_list
-                style = st["latents_fn"](batch_size, m.G.num_layers, z_dim, device=self.device)
-                micro.append(("noise", style, image_noise(batch_size, m.G.image_size, device=self.device), cond))
+                st.latents_fn = mixed_list if random() < self.mixed_prob else noise_list
+                style = st.latents_fn(batch_size, m.G.num_layers, self._z_dim, device=self.device)
+                micro.append(_Micro("noise", image_noise(batch_size, size, device=self.device), latents=style, cond=cond))
                 if self.alternating_training:
-                    st["encoder_input"] = True
+                    st.encoder_input = True
             if fuse:
                 random(), random()  # the two AugWrapper draws of this micro-step (:1331-1333)
-        return reals, micro
+        return _PhaseInputs(micro, reals=reals)
 
     def _draw_g(self, group, st, fuse, apply_pl):
         """Generator-phase inputs of one group (:1376-1421): loader batch (drawn on noise micro-steps too), image
         noise / latents, the AugWrapper draw, and the path-length noise where the reference draws it."""
-        m = self.StylEx
-        batch_size = math.ceil(self.batch_size / self.world_size)
-        micro, pl_noises = [], []
+        m, batch_size = self.StylEx, self._rank_batch
+        micro, pl_noises, size = [], [], m.G.image_size
         for _ in group:
             batch = self._next_batch()
-            if (not self.alternating_training) or st["encoder_input"]:
-                micro.append(("enc", batch, image_noise(batch_size, m.G.image_size, device=self.device), batch))
+            if (not self.alternating_training) or st.encoder_input:
+                micro.append(_Micro("enc", image_noise(batch_size, size, device=self.device), batch=batch, cond=batch))
             else:
-                z_dim = m.G.latent_dim - (m.num_classes if self.new_architecture else 0)
-                style = st["latents_fn"](batch_size, m.G.num_layers, z_dim, device=self.device)
-                micro.append(("noise", style, image_noise(batch_size, m.G.image_size, device=self.device), batch))
+                style = st.latents_fn(batch_size, m.G.num_layers, self._z_dim, device=self.device)
+                micro.append(_Micro("noise", image_noise(batch_size, size, device=self.device), latents=style, cond=batch))
             if fuse:
                 random()  # the AugWrapper draw of this micro-step (:1417)
                 if apply_pl:
-                    pl_noises.append(draw_pl_noise((batch_size, 4 if self.transparent else 3, m.G.image_size,
-                                                    m.G.image_size), self.device))
-            st["encoder_input"] = not st["encoder_input"]
-        return micro, pl_noises
+                    pl_noises.append(draw_pl_noise((batch_size, 4 if self.transparent else 3, size, size), self.device))
+            st.encoder_input = not st.encoder_input
+        return _PhaseInputs(micro, pl_noises=pl_noises)
 
     # -- device side of a phase: forward + backward of one micro-step group -------------------------------------
 
-    def _d_compute(self, reals, micro, apply_gp, gae, fuse, last, acc):
-        m = self.StylEx
-        aug = {"prob": self.aug_prob, "types": self.aug_types}
-
-        new = self.new_architecture
-
-        def D_call(images, detach=False, probs=None):
-            if fuse:  # AugWrapper at prob 0 is D itself; its random() draw is issued where the reference draws it
-                images = images.detach() if detach else images
-                return m.D(images, probabilities=probs) if new else m.D(images)
-            return m.D_aug(images, detach=detach, probabilities=probs, **aug)
-
-        cond = None
+    def _d_compute(self, inp, apply_gp, gae, fuse, last, acc):
+        m, new, reals = self.StylEx, self.new_architecture, inp.reals
         with torch.no_grad():  # the generator/encoder graph is never used in this phase (:1330-1331)
-            ws, conds = [], []
-            for e in micro:
-                if e[0] == "enc":
-                    _, logits, w = self._styles_from_encoder(e[1])
-                    p_i = F.softmax(logits, dim=1) if new else None
-                else:
-                    # new architecture: probabilities of the micro-step's conditioning batch (:1332-1333, :1352)
-                    p_i = F.softmax(self._classify(e[3]), dim=1) if new else None
-                    w = self._styles_of(e, p_i)
-                ws.append(w)
-                conds.append(p_i)
-            if new:
-                cond = _cat(conds)
+            ws, _, cond = self._micro_styles(inp.micro)
             ops.set_fast(True)
-            generated = m.G(_cat(ws), _cat([e[2] for e in micro]))
+            generated = m.G(_cat(ws), _cat([e.inoise for e in inp.micro]))
         real = _cat(reals)
         n_fake = generated.shape[0]
-        grad_norms = None
-        tangent_gp = False
         if apply_gp:
             import gp_tangent
 
@@ -1046,14 +1068,14 @@ class Trainer:
 
             def fake_branch():
                 ops.set_fast(True)  # the fake branch is only ever differentiated once
-                return D_call(generated, detach=True, probs=cond)
+                return self._D_call(generated, fuse, detach=True, probs=cond)
 
             def real_branch():
                 if tangent_gp:
                     ops.set_fast(True)
                     return gp_tangent.d_real_with_norms(m.D, real)
                 ops.set_fast(False)  # the gradient penalty differentiates the real branch twice
-                return D_call(real, probs=cond)
+                return self._D_call(real, fuse, probs=cond)
 
             # the two D passes of a penalty step are independent until the loss: two HIP streams when D_aug is
             # a pass-through (`fuse`; with augmentation the reference's fake-then-real draw order is kept)
@@ -1070,12 +1092,12 @@ class Trainer:
             # D(fake) and D(real) are one pass over the concatenated batch
             ops.set_fast(True)
             if fuse:
-                both = D_call(torch.cat((generated, real), dim=0), detach=True,
-                              probs=torch.cat((cond, cond), dim=0) if new else None)
+                both = self._D_call(torch.cat((generated, real), dim=0), fuse, detach=True,
+                                    probs=torch.cat((cond, cond), dim=0) if new else None)
                 fake_out, real_out = both[:n_fake], both[n_fake:]
             else:
-                fake_out = D_call(generated, detach=True, probs=cond)
-                real_out = D_call(real, probs=cond)
+                fake_out = self._D_call(generated, fuse, detach=True, probs=cond)
+                real_out = self._D_call(real, fuse, probs=cond)
         disc_loss, lo = 0, 0
         for r in reals:
             sl = slice(lo, lo + r.shape[0])
@@ -1094,37 +1116,15 @@ class Trainer:
             disc_loss.register_hook(raise_if_nan)  # reference :1352 (opt-in: the check synchronises the host)
         disc_loss.backward()
 
-    def _g_compute(self, micro, pl_noises, apply_pl, gae, fuse, last, acc):
-        m = self.StylEx
-        aug = {"prob": self.aug_prob, "types": self.aug_types}
-
-        new = self.new_architecture
-
-        def D_call(images, probs=None):
-            if fuse:
-                return m.D(images, probabilities=probs) if new else m.D(images)
-            return m.D_aug(images, detach=False, probabilities=probs, **aug)
-
-        ws, encs, conds = [], [], []
-        for e in micro:
-            if e[0] == "enc":
-                enc_out, real_logits, w_styles = self._styles_from_encoder(e[1])
-                encs.append((e[1], enc_out, real_logits))
-                p_i = F.softmax(real_logits, dim=1) if new else None
-            else:
-                # new architecture: the classifier runs on the loader batch of EVERY micro-step (:1437-1438)
-                p_i = F.softmax(self._classify(e[3]), dim=1) if new else None
-                w_styles = self._styles_of(e, p_i)
-                encs.append(None)
-            ws.append(w_styles)
-            conds.append(p_i)
-        cond = _cat(conds) if new else None
+    def _g_compute(self, inp, apply_pl, gae, fuse, last, acc):
+        m, new, pl_noises = self.StylEx, self.new_architecture, inp.pl_noises
+        ws, encs, cond = self._micro_styles(inp.micro)
         w_all = _cat(ws)
         # path-length regularisation differentiates the GENERATOR twice (d images / d styles, then the loss on it):
         # only G runs on the composable double-differentiable ops; the encoder above and D / encoder / classifier /
         # LPIPS below are differentiated once and keep the fused path
         ops.set_fast(not apply_pl)
-        generated_all = m.G(w_all, _cat([e[2] for e in micro]))
+        generated_all = m.G(w_all, _cat([e.inoise for e in inp.micro]))
         ops.set_fast(True)
         pl_all = calc_pl_lengths(w_all, generated_all, _cat(pl_noises)) if (apply_pl and pl_noises) else None
         # four independent consumers of the generated batch: D, and per encoder micro-step the classifier,
@@ -1133,7 +1133,7 @@ class Trainer:
         for w_styles in ws:
             spans.append(slice(lo, lo + w_styles.shape[0]))
             lo += w_styles.shape[0]
-        branches, where = [lambda: D_call(generated_all, cond)], []
+        branches, where = [lambda: self._D_call(generated_all, fuse, probs=cond)], []
         for sl, enc in zip(spans, encs):
             if enc is not None:
                 gen_i, batch_i = generated_all[sl], enc[0]
@@ -1194,9 +1194,8 @@ class Trainer:
     def _drain_draw_ahead(self):
         """Wait for (and keep) a prefetched discriminator-phase draw: called before anything else draws from the loader
         or the CPU generators (evaluate, generate_truncated, calculate_fid ...)."""
-        nd = getattr(self, "_next_d", None)
-        if nd is not None:
-            nd[0].exception()  # waits; an exception resurfaces when the next train() call takes the result
+        if self._next_d is not None:
+            self._next_d[0].exception()  # waits; an exception resurfaces when the next train() call takes the result
 
     def _step_ends_with_draws(self):
         """Does THIS train() call end with evaluate / save / FID (which consume loader batches and generator draws)?"""
@@ -1210,7 +1209,7 @@ class Trainer:
         averages — the k smallest; None = all of them.  The reference's own expression on the same variables."""
         if not self.top_k_training:
             return None
-        batch_size = math.ceil(self.batch_size / self.world_size)
+        batch_size = self._rank_batch
         epochs = (self.steps * batch_size * self.gradient_accumulate_every) / len(self.dataset)
         k_frac = max(self.generator_top_k_gamma ** epochs, self.generator_top_k_frac)
         k = math.ceil(batch_size * k_frac)
@@ -1225,6 +1224,7 @@ class Trainer:
         return k
 
     def _new_acc(self):
+        """Loss accumulators of a step on the device; gp: the last micro-step's penalty or None; pl: a host float."""
         acc = {k: torch.zeros((), device=self.device) for k in ("d", "g", "rec", "kl")}
         acc["gp"], acc["pl"] = None, self.pl_mean
         return acc
@@ -1234,8 +1234,8 @@ class Trainer:
         compute (eager mode: the host prepares the next group while the GPU runs this one)."""
         self._zero_grad("D")
         for gi, group in enumerate(groups):
-            reals, micro = inputs[gi] if inputs is not None else self._draw_d(group, st, fuse)
-            self._d_compute(reals, micro, apply_gp, gae, fuse, group is groups[-1], acc)
+            inp = inputs[gi] if inputs is not None else self._draw_d(group, st, fuse)
+            self._d_compute(inp, apply_gp, gae, fuse, group is groups[-1], acc)
 
     def _g_phase(self, groups, inputs, apply_pl, gae, fuse, acc, st=None):
         m = self.StylEx
@@ -1244,18 +1244,15 @@ class Trainer:
         set_requires_grad(m.D, False)  # D weight-gradients of this phase are discarded by :1297 anyway
         try:
             for gi, group in enumerate(groups):
-                micro, pl_noises = inputs[gi] if inputs is not None else self._draw_g(group, st, fuse, apply_pl)
-                self._g_compute(micro, pl_noises, apply_pl, gae, fuse, group is groups[-1], acc)
+                inp = inputs[gi] if inputs is not None else self._draw_g(group, st, fuse, apply_pl)
+                self._g_compute(inp, apply_pl, gae, fuse, group is groups[-1], acc)
         finally:
             set_requires_grad(m.D, True)
             ops.set_fast(False)
 
     def _zero_grad(self, which):
-        m = self.StylEx
-        if self.is_ddp:  # gradients are views of the persistent flat buckets the collectives run on
-            (self._d_sync if which == "D" else self._g_sync).zero_grad()
-        else:
-            (m.D_opt if which == "D" else m.G_opt).zero_grad()
+        m = self.StylEx  # under DDP the gradients are views of the persistent flat buckets the collectives run on
+        ((self._d_sync, self._g_sync) if self.is_ddp else (m.D_opt, m.G_opt))[which == "G"].zero_grad()
 
     def _loss_stack(self, acc):
         gp = acc["gp"]
@@ -1274,23 +1271,21 @@ class Trainer:
         apply_gp = self.steps % self.gp_every == 0
         apply_pl = (not self.no_pl_reg) and self.steps > self.pl_after and self.steps % self.pl_every == 0
 
-        # Micro-step batching: G, D and the encoder carry no batch statistics, so the `gae` micro-steps of a
-        # phase are evaluated as ONE pass over their concatenated batch (same per-sample arithmetic, the
-        # weight-gradient GEMMs sum over gae*B rows at once, half the launches of the launch-bound small
-        # layers).  Inputs are still DRAWN micro-step by micro-step in the reference's order (loader, Python
-        # random(), torch.randn), so every RNG stream is consumed identically.  With augmentation on
-        # (AugWrapper consumes RNG per call) every micro-step stays its own group.
+        # Micro-step batching: G, D and the encoder carry no batch statistics, so the `gae` micro-steps of a phase are
+        # evaluated as ONE pass over their concatenated batch (same per-sample arithmetic, the weight-gradient GEMMs sum over
+        # gae*B rows at once, half the launches of the launch-bound small layers).  Inputs are still DRAWN micro-step by
+        # micro-step in the reference's order (loader, Python random(), torch.randn), so every RNG stream is consumed
+        # identically.  With augmentation on (AugWrapper consumes RNG per call) every micro-step stays its own group.
         fuse = not self.aug_prob
         groups = [list(range(gae))] if fuse else [[i] for i in range(gae)]
-        st = {"encoder_input": False, "latents_fn": None}
+        st = _DrawState()
 
-        self._calls = getattr(self, "_calls", 0) + 1
+        self._calls += 1
         if self._graphs_enabled() and fuse and not apply_pl and not self.new_architecture and self._calls > self.graph_warmup:
-            acc_host = self._train_graphed(groups[0], st, apply_gp, gae)
-            has_gp = apply_gp
+            stack = self._train_graphed(groups[0], st, apply_gp, gae)
         else:
             acc = self._new_acc()
-            stale, self._g_fut = getattr(self, "_g_fut", None), None
+            stale, self._g_fut = self._g_fut, None
             if stale is not None:  # a call that raised (NaN restart) left its generator-phase draw running: let it finish
                 stale.exception()  # before anything else touches the loader / the generators
             # draw-ahead is an eager-path feature: with graphs enabled a draw prefetched here would be neither consumed
@@ -1307,36 +1302,27 @@ class Trainer:
                         d_in, st = res
                 if d_in is None:
                     d_in = self._draw_d(groups[0], st, True)
-                st_g = dict(st)
+                st_g = dataclasses.replace(st)
 
                 def draw_g():
-                    if self.alternating_training:
-                        st_g["encoder_input"] = False
+                    st_g.next_phase(self.alternating_training)
                     return self._draw_g(groups[0], st_g, True, apply_pl)
 
                 g_fut = self._g_fut = self._draw_submit(draw_g)  # the generator phase's inputs, under the discriminator phase
-            # ---------------- discriminator phase ----------------
-            self._d_phase(groups, [d_in] if ahead else None, apply_gp, gae, fuse, acc, st)
-            if self.is_ddp:
-                self._d_sync.all_reduce()
-            self._resolve_losses()  # previous step's scalars: its copy finished long ago, the GPU keeps running
-            self._opt_step(m.D_opt)
-            # ---------------- generator phase ----------------
-            if self.alternating_training:
-                st["encoder_input"] = False
-            g_in = None
-            if ahead:
+
+            def hand_off():
+                st.next_phase(self.alternating_training)
+                if not ahead:
+                    return None  # the generator phase draws its own inputs, group by group
                 g_in = [g_fut.result()]
                 self._g_fut = None
                 if ahead > 1 and not self._step_ends_with_draws():
-                    st_n = {"encoder_input": False, "latents_fn": None}
-                    grp = list(groups[0])
+                    st_n, grp = _DrawState(), list(groups[0])
                     self._next_d = (self._draw_submit(lambda: (self._draw_d(grp, st_n, True), st_n)), sig)
-            self._g_phase(groups, g_in, apply_pl, gae, fuse, acc, st)
-            if self.is_ddp:
-                self._g_sync.all_reduce()
-            self._opt_step(m.G_opt)
-            acc_host, has_gp = self._loss_stack(acc), acc["gp"] is not None
+                return g_in
+
+            stack = self._run_step("eager", groups, [d_in] if ahead else None, None, apply_gp, apply_pl, gae, fuse,
+                                      acc=acc, st=st, hand_off=hand_off)
             if apply_pl and not np.isnan(acc["pl"]):  # EMA(0.99), reference :1128, :1471-1473
                 avg = float(acc["pl"])
                 self.pl_mean = avg if self.pl_mean is None else self.pl_mean * 0.99 + 0.01 * avg
@@ -1344,7 +1330,6 @@ class Trainer:
         # all loss scalars of the step leave in one asynchronous copy (resolved lazily, see _resolve_losses); under
         # DDP a NaN flag, OR-ed over the ranks ON THE DEVICE (no host sync), rides along so that every rank takes the
         # checkpoint-reload path at the same step
-        stack = acc_host
         flag = torch.isnan(stack[:2]).any().to(stack.dtype).reshape(1)
         if self.is_ddp:
             parallel.all_reduce_max_(flag)
@@ -1357,7 +1342,7 @@ class Trainer:
             done.record()
         else:
             host, done = stack, None
-        self._pending = (host, done, has_gp, keep_rec)
+        self._pending = _PendingLosses(host, done, apply_gp, keep_rec)  # a penalty step sets acc["gp"]
         if exists(self.tb_writer):
             for k, v in (("G", self.g_loss), ("D", self.d_loss), ("rec", self.total_rec_loss),
                          ("kl", self.total_kl_loss)):
@@ -1434,114 +1419,127 @@ class Trainer:
         buf.copy_(t, non_blocking=True)
         return buf
 
-    def _bind_micro(self, phase, i, e, layers):
-        if e[0] == "enc":
-            x = self._bind((phase, i, "x"), e[1])
-            return ("enc", x, self._bind((phase, i, "n"), e[2]), x)
-        style = e[1]
+    def _bind_micro(self, phase, i, e):
+        """The static-buffer form of a drawn micro-step.  Both latent buffers and the split are rewritten on every call:
+        a single-latent draw binds its z twice with the split at num_layers (nothing of an earlier mixed draw stays)."""
+        if e.kind == "enc":
+            x = self._bind((phase, i, "x"), e.batch)
+            return _Micro("enc", self._bind((phase, i, "n"), e.inoise), batch=x, cond=x)
+        style = e.latents
         z1 = self._bind((phase, i, "z1"), style[0][0])
         z2 = self._bind((phase, i, "z2"), style[1][0] if len(style) > 1 else style[0][0])
         tt = self._static.get((phase, i, "tt"))
         if tt is None:
             tt = self._static[(phase, i, "tt")] = torch.zeros((), dtype=torch.int64, device=self.device)
-        tt.fill_(style[0][1] if len(style) > 1 else layers)
-        return ("noise_static", (z1, z2, tt), self._bind((phase, i, "n"), e[2]), None)
+        tt.fill_(style[0][1] if len(style) > 1 else self.StylEx.G.num_layers)
+        return _Micro("noise_static", self._bind((phase, i, "n"), e.inoise), latents=(z1, z2, tt))
 
-    def _train_graphed(self, group, st, apply_gp, gae):
-        m = self.StylEx
-        layers = m.G.num_layers
-        # host: every draw of the step in the reference's order, then into the static input buffers.  The previous
-        # replay is still running on the GPU while this happens (stream-ordered copies).
-        reals, micro_d = self._draw_d(group, st, True)
-        if self.alternating_training:
-            st["encoder_input"] = False
-        micro_g, _ = self._draw_g(group, st, True, False)
-        reals = [self._bind(("d", i, "real"), r) for i, r in enumerate(reals)]
-        micro_d = [self._bind_micro("d", i, e, layers) for i, e in enumerate(micro_d)]
-        micro_g = [self._bind_micro("g", i, e, layers) for i, e in enumerate(micro_g)]
-        entry = self._graph_cache.get(apply_gp)
-        if entry is None:
-            self._resolve_losses()
-        if entry is None and apply_gp not in self._graph_warm:
-            # first eligible call of this step shape: run the exact code path of the capture (static input buffers,
-            # device-side layer split) EAGERLY once — every kernel it launches must have been loaded before a capture
-            # starts (a first-time kernel load inside a capture is not capturable)
-            self._graph_warm.add(apply_gp)
-            acc = self._new_acc()
-            self._d_phase([group], [(reals, micro_d)], apply_gp, gae, True, acc)
-            if self.is_ddp:
-                self._d_sync.all_reduce()
-            self._opt_step(m.D_opt)
-            self._g_phase([group], [(micro_g, [])], False, gae, True, acc)
-            if self.is_ddp:
-                self._g_sync.all_reduce()
-            self._opt_step(m.G_opt)
-            self._bump_packs()
-            return self._loss_stack(acc)
-        if entry is None:
-            entry = self._capture(apply_gp, gae, [group], [(reals, micro_d)], [(micro_g, [])])
-            self._graph_cache[apply_gp] = entry
-        resolve = self._pending is not None
-        graphs, out = entry
-        syncs = [self._d_sync.all_reduce, self._g_sync.all_reduce, None] if self.is_ddp else [None, None, None]
-        for gi, (g, sync) in enumerate(zip(graphs, syncs)):
-            g.replay()
-            if gi == 0 and resolve:
-                # previous step's scalars, read where the eager path reads them: AFTER this step's discriminator phase
-                # is queued, so the GPU never runs dry while the host waits for that copy
-                self._resolve_losses()
-            if sync is not None:
-                sync()
-        self._bump_packs()
-        return out
+    # What differs between the four users of _run_step; each entry is what that path did before they shared it.
+    # resolve: where the previous step's scalars are read and a NaN restart is raised — "start": before anything of the
+    #   step is queued; once the D segment is queued (the GPU has work while the host waits for that copy), "d_queued":
+    #   before D's gradient all-reduce and only if a copy is pending, "d_synced": after it.
+    # pack: the D and G segments end in GradSync.pack_all() (captured: every replay refills the flat buckets) instead of
+    #   being followed by GradSync.all_reduce(), which a replay issues between the graphs.
+    # bump: where _bump_packs() runs — before every "segment", between G's optimiser step and the loss "stack", at the "end".
+    _STEP_MODES = {"eager": ("d_synced", False, ()), "warmup": ("start", False, ("stack",)),
+                   "capture": ("start", True, ("segment", "end")), "replay": ("d_queued", False, ("end",))}
 
-    def _capture(self, apply_gp, gae, groups, d_in, g_in):
-        """Capture the step as three HIP graphs (D forward/backward | D step + G forward/backward | G step); under
-        DDP the RCCL gradient all-reduces are issued between the replays."""
-        m = self.StylEx
-        acc = {}
+    def _run_step(self, mode, groups, d_in, g_in, apply_gp, apply_pl, gae, fuse, run=None, acc=None, st=None,
+                  hand_off=None):
+        """THE phase sequence of a step: three segments — D forward/backward | D optimiser step + G forward/backward | G
+        optimiser step + loss stack — and what runs between them (`mode`: a row of _STEP_MODES); returns the loss stack.
+        `run(i, seg)` executes segment i and returns its result: directly (default), into a HIP graph (capture), or it
+        replays that graph without calling `seg` (replay).  Eager only: `acc` — the accumulators exist before the step's
+        draws are queued, elsewhere the D segment makes them (captured: a replay zeroes them again); `d_in` None with
+        `st` — a group's inputs are drawn right before its compute (augmentation on); `hand_off()` — once D's optimiser
+        step is queued: resets the draw state, returns G's inputs (draw-ahead: the worker's draw; submits the next D draw)."""
+        resolve, pack, bump = self._STEP_MODES[mode]
+        m, ddp = self.StylEx, self.is_ddp
 
         def seg_d():
-            acc.update(self._new_acc())
-            self._d_phase(groups, d_in, apply_gp, gae, True, acc)
-            if self.is_ddp:
-                self._d_sync.pack_all()  # captured: every replay refills the flat buckets the collectives run on
+            nonlocal acc
+            acc = self._new_acc() if acc is None else acc
+            self._d_phase(groups, d_in, apply_gp, gae, fuse, acc, st)
+            if ddp and pack:
+                self._d_sync.pack_all()
 
         def seg_g():
-            self._opt_step(m.D_opt)  # + stamp: the generator phase must re-pack D's updated weights inside the capture
-            self._g_phase(groups, g_in, False, gae, True, acc)
-            if self.is_ddp:
+            self._opt_step(m.D_opt)  # + stamp: the generator phase must re-pack D's updated weights (inside a capture too)
+            inputs = hand_off() if hand_off is not None else g_in
+            self._g_phase(groups, inputs, apply_pl, gae, fuse, acc, st)
+            if ddp and pack:
                 self._g_sync.pack_all()
 
         def seg_tail():
             self._opt_step(m.G_opt)
-            acc["out"] = self._loss_stack(acc)
+            if "stack" in bump:
+                self._bump_packs()
+            return self._loss_stack(acc)
 
-        # always three graphs: each phase captures fine on its own, but D phase + G phase in ONE capture with the
-        # branch streams on crashes hipStreamEndCapture (ROCm 7.2, tools/graph_stage_probe.py stage "step")
-        segments = [[seg_d], [seg_g], [seg_tail]]
-        torch.cuda.synchronize()
-        dbg = os.environ.get("STYLEX_GRAPH_DEBUG", "0") == "1"
+        if resolve == "start":
+            self._resolve_losses()
+            if mode == "warmup":
+                self._graph_warm.add(apply_gp)  # not before: a NaN restart raised above leaves the shape unwarmed
+        for i, seg in enumerate((seg_d, seg_g, seg_tail)):
+            if "segment" in bump:
+                self._bump_packs()
+            out = seg() if run is None else run(i, seg)
+            if i == 0 and resolve == "d_queued" and self._pending is not None:
+                self._resolve_losses()
+            if ddp and not pack and i < 2:
+                (self._d_sync, self._g_sync)[i].all_reduce()
+            if i == 0 and resolve == "d_synced":
+                self._resolve_losses()  # its copy finished long ago, the GPU keeps running
+        if "end" in bump:
+            self._bump_packs()
+        return out
+
+    def _train_graphed(self, group, st, apply_gp, gae):
+        # host: every draw of the step in the reference's order, then into the static input buffers.  The previous
+        # replay is still running on the GPU while this happens (stream-ordered copies).
+        d = self._draw_d(group, st, True)
+        st.next_phase(self.alternating_training)
+        g = self._draw_g(group, st, True, False)
+        reals = [self._bind(("d", i, "real"), r) for i, r in enumerate(d.reals)]
+        d_in = [_PhaseInputs([self._bind_micro("d", i, e) for i, e in enumerate(d.micro)], reals=reals)]
+        g_in = [_PhaseInputs([self._bind_micro("g", i, e) for i, e in enumerate(g.micro)])]
+        step = ([group], d_in, g_in, apply_gp, False, gae, True)
+        entry = self._graph_cache.get(apply_gp)
+        if entry is None and apply_gp not in self._graph_warm:
+            # first eligible call of this step shape: run the exact code path of the capture (static input buffers,
+            # device-side layer split) EAGERLY once — every kernel it launches must have been loaded before a capture
+            # starts (a first-time kernel load inside a capture is not capturable)
+            return self._run_step("warmup", *step)
+        if entry is None:
+            # always three graphs: each phase captures fine on its own, but D phase + G phase in ONE capture with the
+            # branch streams on crashes hipStreamEndCapture (ROCm 7.2, tools/graph_stage_probe.py stage "step")
+            graphs = []
+            entry = self._graph_cache[apply_gp] = (graphs, self._run_step("capture", *step, run=self._capture_into(graphs, apply_gp)))
+        graphs, out = entry
+        self._run_step("replay", *step, run=lambda i, seg: graphs[i].replay())
+        return out
+
+    def _capture_into(self, graphs, apply_gp):
+        """Segment runner of _run_step: each segment becomes a HIP graph of its own, appended to `graphs`."""
+        say = print if os.environ.get("STYLEX_GRAPH_DEBUG", "0") == "1" else (lambda *a, **k: None)
         share_pool = os.environ.get("STYLEX_GRAPH_POOL", "1") == "1"
         mode = os.environ.get("STYLEX_GRAPH_MODE", "thread_local")
-        if self._graph_pool is None and share_pool:
-            self._graph_pool = torch.cuda.graph_pool_handle()
-        graphs = []
-        for si, fns in enumerate(segments):
-            self._bump_packs()
+
+        def run(si, seg):
+            if si == 0:
+                torch.cuda.synchronize()
+                if self._graph_pool is None and share_pool:
+                    self._graph_pool = torch.cuda.graph_pool_handle()
             g = torch.cuda.CUDAGraph()
-            if dbg:
-                print("capture: gp=%s segment %d begin" % (apply_gp, si), flush=True)
+            say("capture: gp=%s segment %d begin" % (apply_gp, si), flush=True)
             with torch.cuda.graph(g, pool=self._graph_pool if share_pool else None, capture_error_mode=mode):
-                for fn in fns:
-                    fn()
-                if dbg:
-                    print("capture: segment %d body recorded, ending capture" % si, flush=True)
-            if dbg:
-                print("capture: segment %d done" % si, flush=True)
+                out = seg()
+                say("capture: segment %d body recorded, ending capture" % si, flush=True)
+            say("capture: segment %d done" % si, flush=True)
             graphs.append(g)
-        self._bump_packs()
-        return graphs, acc["out"]
+            return out
+
+        return run
 
     # ---- evaluation / generation (reference :1508-1698) ---------------------------------------
 

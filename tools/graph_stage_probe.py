@@ -192,18 +192,18 @@ def run_stage(name):
         for _ in range(3):
             tr.graphs = False
             tr.train()
-        st_ = {"encoder_input": False, "latents_fn": None}
-        reals, micro_d = tr._draw_d(grp, st_, True)
-        st_["encoder_input"] = False
-        micro_g, _ = tr._draw_g(grp, st_, True, False)
+        st_ = st._DrawState()
+        d_in = tr._draw_d(grp, st_, True)
+        st_.next_phase(True)
+        g_in = tr._draw_g(grp, st_, True, False)
 
         def fn():
             hb.pack_cache_clear()
             acc = tr._new_acc()
             if name.startswith("d_phase"):
-                tr._d_phase([grp], [(reals, micro_d)], name == "d_phase_gp", gae, True, acc)
+                tr._d_phase([grp], [d_in], name == "d_phase_gp", gae, True, acc)
             else:
-                tr._g_phase([grp], [(micro_g, [])], False, gae, True, acc)
+                tr._g_phase([grp], [g_in], False, gae, True, acc)
             return tr._loss_stack(acc)
 
         capture(fn, warm=1)
