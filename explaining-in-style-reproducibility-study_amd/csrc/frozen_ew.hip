@@ -927,8 +927,10 @@ int stylex_conv_image_grad(const float* dy, const float* w, float* dx, const int
     const int64_t nt = (K + S - 1) / S, max_taps = nt * nt;
     const size_t smem = (size_t)(max_taps * ((N + 3) & ~3) * 4 * sizeof(float));  // the largest residue class's weights
     if (smem > 64 * 1024) return STYLEX_EINVAL;
-    if (nt <= 4 && nt >= 2) {  // register-tiled kernel (the two frozen stems: 11 x 11 / 4 -> 3 taps per axis, 7 x 7 / 2 -> 4)
-        const size_t smem_rt = (size_t)(nt * 4 * ((N + 3) & ~3) * 4 * sizeof(float));  // [<= nt tap columns][NT <= 4][N4][4]
+    const size_t smem_rt = (size_t)(nt * 4 * ((N + 3) & ~3) * 4 * sizeof(float));  // [<= nt tap columns][NT <= 4][N4][4]
+    // register-tiled kernel (the two frozen stems: 11 x 11 / 4 -> 3 taps per axis, 7 x 7 / 2 -> 4); its LDS tile is larger than
+    // the generic kernel's for nt < 4 (nt * 4 rows against nt * nt): where it does not fit, the generic kernel runs
+    if (nt <= 4 && nt >= 2 && smem_rt <= 64 * 1024) {
 #define STYLEX_IMG_GRAD_RT(SS, NTT)                                                                                              \
     hipLaunchKernelGGL((conv_image_grad_rt_kernel<SS, NTT>), grid, dim3(256), smem_rt, (hipStream_t)stream, dy, w, dx, (int)N, (int)Ho, \
                        (int)Wo, (int)C, (int)K, (int)pad, (int)Hi, (int)Wi, tiles_w)

@@ -261,6 +261,8 @@ static int modconv_bwd_prep_impl(const void* gy, const void* y, const float* noi
                                  const float* noise_w, const float* noise_b, void* gz, float* partial, const int64_t* sh,
                                  int nchunks, int lrelu, int act_dtype, const float* gz_scale, void* stream) {
     if (act_dtype != 0 && act_dtype != 1) return STYLEX_EINVAL;
+    // 0 = linear, 1 = LeakyReLU(0.2).  No ReLU mode: S0 needs the pre-activation, which y = 0 does not determine
+    if (lrelu != 0 && lrelu != 1) return STYLEX_EINVAL;
     if (!gy || !y || !gz || !partial || !ok_shape(sh, nchunks)) return STYLEX_EINVAL;
     if (noise && (!noise_w || !noise_b || noise_stride < sh[1] || noise_stride < sh[2])) return STYLEX_EINVAL;
     int C = (int)sh[3];

@@ -376,6 +376,7 @@ int stylex_modcoeff_bwd(const float* gd, const float* d, const float* s1, const 
  *      dx may be NULL (reduction only).
  * stylex_modconv_bwd_prep: for y = lrelu(d*z + noise[b,w,h]*nw[c] + nb[c]) (:700-714):
  *      gz = gy * lrelu'(y);  partial[.][0] = sum gz*(d*z), [1] = sum gz*noise, [2] = sum gz
+ *      lrelu is 0 (linear) or 1; anything else (ReLU: y = 0 does not determine d*z) is STYLEX_EINVAL
  * stylex_scale_reduce:     gx = t * s[b][c];  partial = sum_pixels x*t   (gradient wrt style+1, :650) */
 int stylex_reduce_chunks(const int64_t* shape);
 int stylex_act_bwd_reduce(const void* dy, const void* y, void* dx, float* partial, const int64_t* shape, int nchunks,

@@ -1573,7 +1573,8 @@ def test_frozen_tail_kernels_vs_aten(shape):
 
 @pytest.mark.parametrize("case", [(2, 64, 3, 7, 2, 3, 32, 32), (3, 64, 3, 11, 4, 2, 64, 64), (2, 16, 3, 11, 4, 2, 37, 45),
                                   (1, 8, 4, 3, 1, 1, 9, 70), (2, 24, 3, 7, 2, 3, 33, 130), (1, 64, 3, 5, 4, 0, 21, 17),
-                                  (32, 64, 3, 7, 2, 3, 224, 224), (32, 64, 3, 11, 4, 2, 256, 256)])
+                                  (32, 64, 3, 7, 2, 3, 224, 224), (32, 64, 3, 11, 4, 2, 256, 256),
+                                  (1, 384, 3, 3, 1, 1, 9, 9)])  # 3 taps per axis, N = 384: the register tile's LDS > 64 KB -> generic kernel
 def test_image_gradient_kernel_of_the_frozen_stems(case, monkeypatch):
     """stylex_conv_image_grad (round 6): the input gradient of the K x K / stride-S stem convolutions of the frozen classifier
     (ResNet conv1) and LPIPS-AlexNet against torch.nn.grad.conv2d_input in float64 — every residue class of the stride,
