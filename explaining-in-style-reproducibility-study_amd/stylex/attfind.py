@@ -1,6 +1,15 @@
-"""Batched AttFind StyleSpace sweep — drop-in for ``attfind_extraction`` of the reference's
-``stylex/run_attfind_combined.ipynb`` (cell 5, :246-417; "old architecture" branch), producing the same datasets
-(``style_change, latents, base_prob, minima, maxima, style_coordinates, original_images, noise, discriminator``).
+"""Batched AttFind StyleSpace sweep — drop-in for the extraction cell of the reference's
+``stylex/run_attfind_combined.ipynb`` (cell 5, :246-417), producing the same datasets (``style_change, latents,
+base_prob, minima, maxima, style_coordinates, original_images, noise, discriminator``), for BOTH architectures the
+notebook switches between with ``USE_OLD_ARCHITECTURE``:
+
+* default: ``w = cat(encoder, logits)``, ``D(generated)``;
+* conditional (``StylEx(conditional=True)``, the notebook's ``faces_new``): ``w = cat(encoder, softmax(logits))`` and
+  ``D(generated, probabilities=softmax(classify(generated)))``; ``base_prob`` stays the raw logits.
+
+``attfind_extraction`` / ``find_discriminator_threshold`` read the architecture from ``stylex.conditional``; everything
+after the first pass (the sweep, ``change_images``, the ``visualize_*`` functions) works on the stored latents and has
+no branch, like the notebook's cells 17-21.  ``load_records`` is cell 12's loader, ``attfind_cli.py`` the command line.
 
 The notebook perturbs ONE style coordinate at a time by mutating ``to_style{1,2}.bias`` in place and re-running
 the whole generator at batch 1: 2 x N_coords generator + classifier evaluations per image (2 x 2464 at 64 px).
@@ -13,7 +22,9 @@ Here the same arithmetic is restructured for the GPU:
 * ``chunk`` perturbations (both directions of chunk/2 coordinates) run as one generator-suffix + classifier pass;
 * under ``torch.distributed`` the sweep shards over images: every rank runs the cheap first pass on
   all images (1 evaluation each, so minima / maxima need no collective), sweeps images ``rank::world`` and one
-  ``all_reduce(SUM)`` over the effect tensor (zero for foreign images) assembles the result on every rank.
+  ``all_reduce(SUM)`` over the effect tensor (zero for foreign images) assembles the result on every rank;
+* ``first_pass_batch`` > 1 runs that first pass (encoder, classifier, generator, discriminator, classifier of the
+  generated image) on several loader items at once; 1, the default, is the notebook's batch-1 loop launch for launch.
 """
 import os
 
@@ -62,31 +73,76 @@ def _suffix(G, k, x, rgb, w_tensor, noise, styles_k):
     return rgb.float()
 
 
+def _loader_groups(images, size):
+    """Lists of up to size() loader items ([1,3,S,S] each), in loader order; size() is asked before every group."""
+    it = iter(images)
+    while True:
+        group = []
+        for _ in range(size()):
+            item = next(it, None)
+            if item is None:
+                break
+            group.append(item)
+        if not group:
+            return
+        yield group
+
+
+def _first_pass(stylex, classifier, group, noise, conditional):
+    """Cell 5's per-image first pass for a list of [1,3,S,S] items run as ONE batch: (batch, w, generated image, style
+    coordinates, discriminator output [b], logits of the generated image or None).  The conditional discriminator needs
+    the generated image's probabilities, so there the logits are always computed; the default architecture leaves them
+    to the caller (only kept images need them)."""
+    G = stylex.G
+    dev = noise.device
+    batch = group[0].to(dev) if len(group) == 1 else torch.cat([t.to(dev) for t in group])
+    b = batch.shape[0]
+    enc = stylex.encoder(batch).reshape(b, -1)
+    logits = classifier.classify_images(batch)
+    w = torch.cat((enc, torch.softmax(logits, dim=1) if conditional else logits), dim=1)
+    generated, sc = G(styles_def_to_tensor([(w, G.num_layers)]), noise.expand(b, -1, -1, -1), get_style_coords=True)
+    gen_logits = None
+    if conditional:
+        gen_logits = classifier.classify_images(generated)
+        d_out = stylex.D(generated, probabilities=torch.softmax(gen_logits, dim=1))
+    else:
+        d_out = stylex.D(generated)
+    return batch, w, generated, sc, d_out.reshape(b), gen_logits
+
+
+def _conditional(stylex, conditional):
+    return bool(getattr(stylex, "conditional", False)) if conditional is None else bool(conditional)
+
+
 @torch.no_grad()
 def attfind_extraction(stylex, classifier, images, num_images, noise, shift_size=1.0, discriminator_threshold=None,
-                       use_discriminator=False, chunk=256, results_folder=None):
+                       use_discriminator=False, chunk=256, results_folder=None, conditional=None, first_pass_batch=1):
     """images: iterable of [1,3,S,S] batches (the notebook's batch-size-1 loader).  Returns a dict of CPU tensors
-    with the notebook's dataset names; with `results_folder` also writes style_change_records.{hdf5|npz}."""
+    with the notebook's dataset names; with `results_folder` also writes style_change_records.{hdf5|npz}.
+    `conditional`: None reads ``stylex.conditional``.  `use_discriminator` drops an image whose discriminator output is
+    below `discriminator_threshold` (the notebook's own ``skip`` flag is inverted; not copied).  `first_pass_batch`
+    loader items go through the first pass together; images are kept, and counted towards `num_images`, in loader order."""
     G = stylex.G
     dev = next(G.parameters()).device
     noise = noise.to(dev)
+    conditional = _conditional(stylex, conditional)
+    filtering = use_discriminator and discriminator_threshold is not None
     n_coords = sum(b.num_style_coords for b in G.blocks)
     latents, base_logits, coords, disc, originals = [], [], [], [], []
-    for batch in images:
-        if len(latents) >= num_images:
-            break
-        batch = batch.to(dev)
-        enc = stylex.encoder(batch).reshape(1, -1)
-        w = torch.cat((enc, classifier.classify_images(batch)), dim=1)
-        generated, sc = G(styles_def_to_tensor([(w, G.num_layers)]), noise, get_style_coords=True)
-        d_out = stylex.D(generated).reshape(1)
-        if use_discriminator and discriminator_threshold is not None and float(d_out) < discriminator_threshold:
-            continue
-        originals.append(batch[0])
-        latents.append(w[0])
-        coords.append(sc[0])
-        disc.append(d_out)
-        base_logits.append(classifier.classify_images(generated)[0])
+    # never more items in a group than images still wanted: a group cannot keep past num_images
+    for group in _loader_groups(images, lambda: min(first_pass_batch, num_images - len(latents))):
+        batch, w, generated, sc, d_out, gen_logits = _first_pass(stylex, classifier, group, noise, conditional)
+        keep = list(range(batch.shape[0]))
+        if filtering:
+            keep = [j for j, d in enumerate(d_out.tolist()) if not d < discriminator_threshold]
+        if keep and gen_logits is None:
+            gen_logits = classifier.classify_images(generated)
+        for j in keep:
+            originals.append(batch[j])
+            latents.append(w[j])
+            coords.append(sc[j])
+            disc.append(d_out[j:j + 1])
+            base_logits.append(gen_logits[j])
     if not latents:
         raise ValueError("No images pass the threshold check")
     n = len(latents)
@@ -133,16 +189,73 @@ def attfind_extraction(stylex, classifier, images, num_images, noise, shift_size
     return out
 
 
-def write_records(out, results_folder):
-    """style_change_records.hdf5 with the notebook's dataset names (:392-416); .npz when h5py is not installed."""
+def _write_datasets(datasets, folder, stem):
+    """<stem>.hdf5 with one float dataset per entry; <stem>.npz when h5py is not installed."""
     try:
         import h5py
     except ImportError:
-        np.savez(os.path.join(results_folder, "style_change_records.npz"), **{k: v.numpy() for k, v in out.items()})
+        np.savez(os.path.join(folder, stem + ".npz"), **{k: v.numpy() for k, v in datasets.items()})
         return
-    with h5py.File(os.path.join(results_folder, "style_change_records.hdf5"), "w") as f:
-        for k in DATASETS:
-            f.create_dataset(k, data=out[k].numpy(), dtype="f")
+    with h5py.File(os.path.join(folder, stem + ".hdf5"), "w") as f:
+        for k, v in datasets.items():
+            f.create_dataset(k, data=v.numpy(), dtype="f")
+
+
+def _read_datasets(folder, stem):
+    path = os.path.join(folder, stem + ".hdf5")
+    if os.path.isfile(path):
+        import h5py
+
+        with h5py.File(path, "r") as f:
+            return {k: np.array(f[k]) for k in f.keys()}
+    with np.load(os.path.join(folder, stem + ".npz")) as f:
+        return {k: f[k] for k in f.files}
+
+
+def write_records(out, results_folder):
+    """style_change_records.hdf5 with the notebook's dataset names (:392-416); .npz when h5py is not installed."""
+    _write_datasets({k: out[k] for k in DATASETS}, results_folder, "style_change_records")
+
+
+def load_records(results_folder, threshold_index=None):
+    """Cell 12: the arrays of style_change_records.{hdf5|npz} under their dataset names — the per-image ones truncated
+    to the first `threshold_index` rows (``load_hdf5_results``), `noise` as stored, `minima` / `maxima` squeezed — plus
+    `distances`, the [images, coords, 2] distances of every style coordinate to its minimum / maximum."""
+    f = _read_datasets(results_folder, "style_change_records")
+    out = {k: f[k][0:threshold_index] for k in ("style_change", "latents", "base_prob", "style_coordinates",
+                                                "original_images", "discriminator")}
+    out["noise"] = f["noise"]
+    out["minima"], out["maxima"] = np.squeeze(f["minima"]), np.squeeze(f["maxima"])
+    out["distances"] = style_vector_distances(out["style_coordinates"], out["minima"], out["maxima"])
+    return out
+
+
+THRESHOLD_DATASETS = ("discriminator_outputs", "generated_images")
+
+
+@torch.no_grad()
+def find_discriminator_threshold(stylex, classifier, images, num_images, noise, conditional=None, threshold_folder=None,
+                                 first_pass_batch=1):
+    """Cell 5's ``find_discriminator_threshold``: the discriminator output [n, 1] and the generated image [n, 3, S, S]
+    of the first `num_images` loader items (CPU float tensors), from which a caller picks `discriminator_threshold`.
+    With `threshold_folder` also writes discriminator_threshold.{hdf5|npz} under those two dataset names."""
+    dev = next(stylex.G.parameters()).device
+    noise = noise.to(dev)
+    conditional = _conditional(stylex, conditional)
+    disc, generated_images = [], []
+    found = 0
+    for group in _loader_groups(images, lambda: min(first_pass_batch, num_images - found)):
+        _, _, generated, _, d_out, _ = _first_pass(stylex, classifier, group, noise, conditional)
+        disc.append(d_out[:, None])
+        generated_images.append(generated)
+        found += d_out.shape[0]
+    if not disc:
+        raise ValueError("The loader holds no images")
+    out = {"discriminator_outputs": torch.cat(disc), "generated_images": torch.cat(generated_images)}
+    out = {k: v.detach().float().cpu() for k, v in out.items()}
+    if threshold_folder is not None:
+        _write_datasets(out, threshold_folder, "discriminator_threshold")
+    return out
 
 
 def find_significant_styles(style_change_effect, num_indices, class_index, max_image_effect=0.2, sindex_offset=0):
