@@ -2,13 +2,15 @@
 // 3x3 reflect blur and its adjoint, bias(+noise)+LeakyReLU and its gradient mask, row-wise
 // squared norms, even-pixel gather.  Tensors NHWC, fp32 or bf16 (act_dtype); one lane handles VEC consecutive
 // channels of a pixel (4 fp32 / 8 bf16 = 16 bytes, or 1 for odd channel counts) so that a wave reads/writes whole
-// lines.  Grid-stride loops.  bf16 blurs take the column-strip kernel below (5 TB/s vs 2-3 for the direct form).
+// lines.  Grid-stride loops.  bf16 blurs and the bf16 bilinear x2 pair take the column-strip kernels below (5 TB/s vs 2-3
+// for the direct forms).
 //
 // Reference ops replaced (file stylex/stylex_train.py): nn.Upsample(scale_factor=2, bilinear,
 // align_corners=False) :614,679; Blur :144-153 (kornia filter2d, reflect); nn.Conv2d bias +
 // leaky_relu(0.2) :340-341,726-731; noise add :696-714; gradients.norm(2, dim=1) :302.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "stylex_internal.h"
 
@@ -151,6 +153,125 @@ __global__ void upsample2x_bwd_kernel(const void* __restrict__ dy, void* __restr
             }
         }
         Vec<V>::st(dx, pix * C + c, acc, bf);
+    }
+}
+
+// ---- bilinear x2 as column strips (bf16, C % 8 == 0; the pattern of blur3x3_strip_kernel below) ---------------------
+// A thread owns 8 channels of one INPUT column and walks ROWS input rows.  Per input row it forms the two horizontally
+// combined vectors (even / odd output column) once, from three loads, keeps the previous row's pair in registers and
+// writes the 2 x 2 outputs of the pixel: 3 loads and no division per 4 stores, where the direct form above spends 16 loads
+// and 12 divisions.  The fma sequence per output is the direct kernel's, so the outputs are the same bits.  Offsets inside
+// an image are 32-bit (checked by the host).
+struct UpPair {
+    F8 e, o;
+};
+template <int ROWS>
+__global__ __launch_bounds__(256) void upsample2x_fwd_strip_kernel(const unsigned short* __restrict__ x,
+                                                                   unsigned short* __restrict__ y, int B, int H, int W, int C) {
+    const int cv = C >> 3;
+    const int strips = (H + ROWS - 1) / ROWS;
+    const long total = (long)B * strips * W * cv;
+    const int rs = W * C, ors = 2 * W * C;  // input / output row stride in elements
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        int cq, w, hs, b;
+        decomp_index(i, cv, W, strips, cq, w, hs, b);
+        const int h0 = hs * ROWS;
+        const unsigned short* xin = x + (long)b * H * rs + cq * 8;
+        unsigned short* yout = y + (long)b * 2 * H * ors + 2 * w * C + cq * 8;
+        const int ol = max(w - 1, 0) * C, om = w * C, orr = min(w + 1, W - 1) * C;
+        auto hpair = [&](int hh) -> UpPair {  // row hh (a valid index) combined for output columns 2w and 2w + 1
+            const int ro = hh * rs;
+            const F8 l = Vec<8>::ld(xin, ro + ol, 1), m = Vec<8>::ld(xin, ro + om, 1), r = Vec<8>::ld(xin, ro + orr, 1);
+            UpPair p{Vec<8>::zero(), Vec<8>::zero()};
+            Vec<8>::fma(p.e, 1.f - 0.75f, l);
+            Vec<8>::fma(p.e, 0.75f, m);
+            Vec<8>::fma(p.o, 1.f - 0.25f, m);
+            Vec<8>::fma(p.o, 0.25f, r);
+            return p;
+        };
+        auto vmix = [&](float wlo, const F8& lo, float whi, const F8& hi, int off) {
+            F8 acc = Vec<8>::zero();
+            Vec<8>::fma(acc, wlo, lo);
+            Vec<8>::fma(acc, whi, hi);
+            Vec<8>::st(yout, off, acc, 1);
+        };
+        UpPair prev = hpair(max(h0 - 1, 0)), cur = hpair(h0);
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const int h = h0 + r;
+            if (h >= H) break;
+            const UpPair next = hpair(min(h + 1, H - 1));
+            const int o0 = 2 * h * ors;
+            vmix(1.f - 0.75f, prev.e, 0.75f, cur.e, o0);  // output row 2h:     .25 in[h-1] + .75 in[h]
+            vmix(1.f - 0.75f, prev.o, 0.75f, cur.o, o0 + C);
+            vmix(1.f - 0.25f, cur.e, 0.25f, next.e, o0 + ors);  // output row 2h + 1: .75 in[h] + .25 in[h+1]
+            vmix(1.f - 0.25f, cur.o, 0.25f, next.o, o0 + ors + C);
+            prev = cur;
+            cur = next;
+        }
+    }
+}
+
+// The adjoint likewise: a thread owns 8 channels of one column of dx and walks ROWS of its rows.  Row ih sums the 4 x 4
+// window of dy rows 2ih-1 .. 2ih+2; two of them are the previous row's last two, kept (packed, 4 registers per vector) in
+// registers, so every dy row is loaded once per strip.  Taps are added in the direct kernel's order (rows outer, columns
+// inner, out-of-range taps skipped) with its coefficients: the same bits.
+template <int ROWS>
+__global__ __launch_bounds__(256) void upsample2x_bwd_strip_kernel(const unsigned short* __restrict__ dy,
+                                                                   unsigned short* __restrict__ dx, int B, int H, int W, int C) {
+    const int cv = C >> 3;
+    const int strips = (H + ROWS - 1) / ROWS;
+    const long total = (long)B * strips * W * cv;
+    const int rs = W * C, ors = 2 * W * C;  // dx / dy row stride in elements
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        int cq, iw, hs, b;
+        decomp_index(i, cv, W, strips, cq, iw, hs, b);
+        const int h0 = hs * ROWS;
+        const uint4* src = reinterpret_cast<const uint4*>(dy + (long)b * 2 * H * ors + cq * 8);
+        unsigned short* dst = dx + (long)b * H * rs + iw * C + cq * 8;
+        int oc[4];    // column offsets of the window, in 16-byte vectors (clamped: a skipped tap still loads in bounds)
+        float cw[4];  // 0 marks a tap the direct kernel skips
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int ow = 2 * iw + e - 1;
+            const bool in = ow >= 0 && ow < 2 * W;
+            cw[e] = in ? up_coef(ow, iw, W) : 0.f;
+            oc[e] = (min(max(ow, 0), 2 * W - 1) * C) >> 3;
+        }
+        auto ldrow = [&](int oh, uint4 (&v)[4]) {
+            const int ro = (min(max(oh, 0), 2 * H - 1) * ors) >> 3;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = src[ro + oc[e]];
+        };
+        uint4 win[4][4];
+        ldrow(2 * h0 - 1, win[0]);
+        ldrow(2 * h0, win[1]);
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const int ih = h0 + r;
+            if (ih >= H) break;
+            ldrow(2 * ih + 1, win[2]);
+            ldrow(2 * ih + 2, win[3]);
+            F8 acc = Vec<8>::zero();
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const int oh = 2 * ih + a - 1;
+                const float ch = (oh >= 0 && oh < 2 * H) ? up_coef(oh, ih, H) : 0.f;
+                if (ch == 0.f) continue;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (cw[e] == 0.f) continue;
+                    const uint4 q = win[a][e];
+                    Vec<8>::fma(acc, ch * cw[e], F8{act_unpack4(make_uint2(q.x, q.y)), act_unpack4(make_uint2(q.z, q.w))});
+                }
+            }
+            Vec<8>::st(dst, ih * rs, acc, 1);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                win[0][e] = win[2][e];
+                win[1][e] = win[3][e];
+            }
+        }
     }
 }
 
@@ -569,6 +690,20 @@ static int launch_blur_strip(const void* in, void* out, int B, int H, int W, int
     return (int)hipGetLastError();
 }
 
+// Strip forms of the bilinear x2 pair: bf16, whole 16-byte vectors, at least one full strip of rows, 32-bit offsets inside
+// an image.  STYLEX_UPSAMPLE_STRIP=0 selects the direct kernels (read per launch: A/B tests toggle it in-process).
+constexpr int UP_ROWS = 8;
+static bool up_strip_ok(int bf, int H, int W, int C, const void* a, const void* b) {
+    const char* env = getenv("STYLEX_UPSAMPLE_STRIP");
+    return bf && (C % 8 == 0) && H >= UP_ROWS && (long)4 * H * W * C < (1L << 31) && !(env && env[0] == '0') &&
+           ((reinterpret_cast<uintptr_t>(a) & 15) == 0) && ((reinterpret_cast<uintptr_t>(b) & 15) == 0);
+}
+static unsigned up_strip_blocks(int B, int H, int W, int C) {
+    long work = (long)B * ((H + UP_ROWS - 1) / UP_ROWS) * W * (C / 8);
+    long blocks = (work + 255) / 256;
+    return (unsigned)(blocks > 16384 ? 16384 : blocks);
+}
+
 extern "C" {
 
 #define EW_ARGS const int64_t* sh, int act_dtype, void* stream
@@ -581,11 +716,21 @@ extern "C" {
 int stylex_upsample2x_bilinear_fwd(const void* x, void* y, EW_ARGS) {
     EW_UNPACK
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return STYLEX_EINVAL;
+    if (up_strip_ok(bf, H, W, C, x, y)) {
+        hipLaunchKernelGGL(upsample2x_fwd_strip_kernel<UP_ROWS>, dim3(up_strip_blocks(B, H, W, C)), dim3(256), 0, s,
+                           (const unsigned short*)x, (unsigned short*)y, B, H, W, C);
+        return (int)hipGetLastError();
+    }
     LAUNCH_EW(upsample2x_fwd_kernel, (long)B * 4 * H * W * C, x, y, x, y, B, H, W, C, bf);
 }
 int stylex_upsample2x_bilinear_bwd(const void* dy, void* dx, EW_ARGS) {
     EW_UNPACK
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return STYLEX_EINVAL;
+    if (up_strip_ok(bf, H, W, C, dy, dx)) {
+        hipLaunchKernelGGL(upsample2x_bwd_strip_kernel<UP_ROWS>, dim3(up_strip_blocks(B, H, W, C)), dim3(256), 0, s,
+                           (const unsigned short*)dy, (unsigned short*)dx, B, H, W, C);
+        return (int)hipGetLastError();
+    }
     LAUNCH_EW(upsample2x_bwd_kernel, (long)B * H * W * C, dy, dx, dy, dx, B, H, W, C, bf);
 }
 int stylex_rgb_up_blur_add_fwd(const void* rgb, const void* prev, void* y, EW_ARGS) {

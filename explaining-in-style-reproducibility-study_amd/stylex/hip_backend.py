@@ -104,6 +104,8 @@ SIGNATURES = {
                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "stylex_modconv_bwd_prep_scaled": (ctypes.c_int, [_c_f, _c_f, _c_f, ctypes.c_int64, _c_f, _c_f, _c_f, _c_f, _c_f, _i64p,
                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_modconv_bwd_prep_nat": (ctypes.c_int, [_c_f, _c_f, _c_f, ctypes.c_int64, _c_f, _c_f, _c_f, _c_f, _c_f, _i64p,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "stylex_scale_reduce": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _i64p, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_void_p]),
     "stylex_pad_rgb8": (ctypes.c_int, [_c_f, _c_f, _i64p, _i64p, ctypes.c_int, ctypes.c_void_p]),
@@ -198,6 +200,17 @@ class StylexHipError(RuntimeError):
     pass
 
 
+# Entry points a library built from an older commit may lack when it is loaded through STYLEX_HIP_LIB for an A/B run; their
+# callers ask has_symbol() and keep the form that library has (another HIP kernel, never an eager fallback).
+OPTIONAL_SYMBOLS = frozenset(["stylex_modconv_bwd_prep_nat"])
+_MISSING_OPTIONAL = set()
+
+
+def has_symbol(name):
+    load_library()
+    return name not in _MISSING_OPTIONAL
+
+
 def load_library(path=None):
     """Load libstylex_hip.so and bind every symbol the header declares.  Raises if absent."""
     global _lib
@@ -208,7 +221,11 @@ def load_library(path=None):
         raise StylexHipError("libstylex_hip.so not found at %s — run `python __graft_entry__.py build` "
                              "(there is no CPU fallback for the product path)" % path)
     lib = ctypes.CDLL(path)
+    _MISSING_OPTIONAL.clear()
     for name, (res, args) in SIGNATURES.items():
+        if name in OPTIONAL_SYMBOLS and path != LIB_PATH and not hasattr(lib, name):
+            _MISSING_OPTIONAL.add(name)  # an older build given by STYLEX_HIP_LIB (A/B runs); the tree's own library has all
+            continue
         fn = getattr(lib, name)  # AttributeError => ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args
@@ -1558,9 +1575,10 @@ def act_bwd_reduce(dy, y, lrelu, scale=1.0, want_dx=True, want_sum=True, per_sam
     return dx, ((partial.sum(dim=1) if per_sample else partial.sum(dim=(0, 1))) if want_sum else None)
 
 
-def modconv_bwd_prep(gy, y, noise, noise_w, noise_b, lrelu, gz_scale=None):
+def modconv_bwd_prep(gy, y, noise, noise_w, noise_b, lrelu, gz_scale=None, noise_natural=False):
     """gz = gy*lrelu'(y); returns gz and S[3][B][C] = per-image sums (gz*(d*z), gz*noise, gz).  With gz_scale [B,C]
-    (the demodulation coefficient) the returned tensor is gz * gz_scale (the sums stay those of gz)."""
+    (the demodulation coefficient) the returned tensor is gz * gz_scale (the sums stay those of gz).
+    noise_natural: `noise` is the plane in natural order, noise[b][h][w] (ops._natural_noise), not the transposed read."""
     lib = _ensure_device(gy)
     assert is_cl(gy) and is_cl(y) and gy.dtype == y.dtype
     b, c, h, w = gy.shape
@@ -1573,7 +1591,13 @@ def modconv_bwd_prep(gy, y, noise, noise_w, noise_b, lrelu, gz_scale=None):
     if noise is not None:
         ns = noise.shape[1]
     lr = 2 if lrelu == "relu" else int(bool(lrelu))
-    if gz_scale is None:
+    if noise_natural:
+        assert noise is not None
+        gz_scale = _f32(gz_scale)
+        _check(lib.stylex_modconv_bwd_prep_nat(_ptr(gy), _ptr(y), _ptr(noise), ns, _ptr(noise_w), _ptr(noise_b),
+                                               _ptr(gz_scale), _ptr(gz), _ptr(partial), shp, nch, lr, _adt(gy), _stream()),
+               "stylex_modconv_bwd_prep_nat")
+    elif gz_scale is None:
         _check(lib.stylex_modconv_bwd_prep(_ptr(gy), _ptr(y), _ptr(noise), ns, _ptr(noise_w), _ptr(noise_b), _ptr(gz),
                                            _ptr(partial), shp, nch, lr, _adt(gy), _stream()), "stylex_modconv_bwd_prep")
     else:

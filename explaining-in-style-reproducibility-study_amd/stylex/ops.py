@@ -621,21 +621,28 @@ class _ModConvFast(torch.autograd.Function):
         else:
             y = hb.conv2d_fwd(x_in, w, 1, pad, _PRECISION, in_scale=s_in, out_scale=d, noise=noise, noise_w=nw, noise_b=nb,
                               lrelu=lrelu)
-        ctx.save_for_backward(x, s1, d, w, noise, nw, nb, y if (lrelu or d is not None or noise is not None) else None)
+        ctx.save_for_backward(x, s1, d, w, noise, nw, nb, y if (lrelu or d is not None or noise is not None) else None,
+                              noise_nat)
         ctx.cfg = (pad, lrelu)
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        x, s1, d, w, noise, nw, nb, y = ctx.saved_tensors
+        x, s1, d, w, noise, nw, nb, y, noise_nat = ctx.saved_tensors
         pad, lrelu = ctx.cfg
         gy = _cl(gy)
         gd = gnw = gnb = None
         folded = False  # gz already carries the demodulation coefficient d
         if y is not None and _reducible(gy.shape[1]):
             fold = d is not None and _PRECISION != hb.F32 and os.environ.get("STYLEX_FOLD_D", "1") != "0"
-            gz, sums = hb.modconv_bwd_prep(gy, y, noise, nw, nb, lrelu, gz_scale=d if fold else None)
+            # the plane the forward read: rows of the plane instead of a strided gather (a library from before the entry
+            # point — STYLEX_HIP_LIB=<older build>, A/B runs — keeps the transposed plane)
+            if noise_nat is not None and hb.has_symbol("stylex_modconv_bwd_prep_nat"):
+                gz, sums = hb.modconv_bwd_prep(gy, y, noise_nat, nw, nb, lrelu, gz_scale=d if fold else None,
+                                               noise_natural=True)
+            else:
+                gz, sums = hb.modconv_bwd_prep(gy, y, noise, nw, nb, lrelu, gz_scale=d if fold else None)
             folded = fold
             if d is not None:
                 gd = sums[:, 0] / d

@@ -178,7 +178,9 @@ int stylex_conv2d_bwd_weight_ex(const void* x, const void* dy, float* dw, float*
  *
  * Bilinear x2, align_corners=False (nn.Upsample, stylex_train.py:614,679) and its adjoint.
  * shape = {B, H, W, C} of the LOW-resolution tensor.  Index rule (exact):
- *   out[2k] = .25*in[max(k-1,0)] + .75*in[k];  out[2k+1] = .75*in[k] + .25*in[min(k+1,n-1)] */
+ *   out[2k] = .25*in[max(k-1,0)] + .75*in[k];  out[2k+1] = .75*in[k] + .25*in[min(k+1,n-1)]
+ * bf16 tensors with C % 8 == 0, H >= 8 and 16-byte aligned pointers take column-strip kernels (same results bit for
+ * bit; STYLEX_UPSAMPLE_STRIP=0 selects the direct kernels). */
 int stylex_upsample2x_bilinear_fwd(const void* x, void* y, const int64_t* shape, int act_dtype, void* stream);
 int stylex_upsample2x_bilinear_bwd(const void* dy, void* dx, const int64_t* shape, int act_dtype, void* stream);
 
@@ -369,6 +371,9 @@ int stylex_modcoeff_bwd(const float* gd, const float* d, const float* s1, const 
  * reductions into ONE pass.  Tensors NHWC fp32, shape = {B, H, W, C}, C % 4 == 0, C <= 1024.
  * Each launch writes partial[b][chunk][k][C] with nchunks = stylex_reduce_chunks(shape); the caller
  * sums over chunks (and over b where the parameter is per channel).  Deterministic.
+ * stylex_modconv_bwd_prep* and stylex_scale_reduce: bf16 tensors with C % 8 == 0 and 16-byte aligned pointers take
+ * lanes of 8 channels (one 16-byte access per tensor and pixel) in the 4-channel geometry: same outputs and same sums, bit for bit.  STYLEX_GLUE_WIDE=0 keeps the
+ * 4-channel lanes.
  *
  * stylex_act_bwd_reduce:   dx = dy * scale * (lrelu ? (y>0 ? 1 : slope) : 1), slope = .2 (lrelu==1) or 0 (lrelu==2, ReLU);
  *                          partial = sum_pixels dx
@@ -391,6 +396,14 @@ int stylex_modconv_bwd_prep_scaled(const void* gy, const void* y, const float* n
                                    const float* noise_w, const float* noise_b, const float* gz_scale, void* gz,
                                    float* partial, const int64_t* shape, int nchunks, int lrelu, int act_dtype,
                                    void* stream);
+/* Same as stylex_modconv_bwd_prep[_scaled] (gz_scale may be NULL), reading the noise plane in NATURAL order,
+ * noise[b][h][w] with row stride noise_stride: the plane the forward epilogue of the modulated conv read
+ * (noise_natural of stylex_conv2d_fwd), one contiguous row per pixel row instead of a strided gather.  Same values,
+ * same sums. */
+int stylex_modconv_bwd_prep_nat(const void* gy, const void* y, const float* noise, int64_t noise_stride,
+                                const float* noise_w, const float* noise_b, const float* gz_scale, void* gz,
+                                float* partial, const int64_t* shape, int nchunks, int lrelu, int act_dtype,
+                                void* stream);
 int stylex_scale_reduce(const void* x, const void* t, const float* s, void* gx, float* partial, const int64_t* shape,
                         int nchunks, int act_dtype, void* stream);
 
