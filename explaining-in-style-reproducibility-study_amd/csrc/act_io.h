@@ -11,6 +11,7 @@ __device__ __forceinline__ unsigned act_pack2(float lo, float hi) {
     act_bf16x2_t r = __builtin_convertvector(v, act_bf16x2_t);  // v_cvt_pk_bf16_f32 (RNE)
     return *reinterpret_cast<unsigned*>(&r);
 }
+__device__ __forceinline__ unsigned short act_bf16_1(float v) { return (unsigned short)(act_pack2(v, 0.f) & 0xffffu); }  // one value (RNE)
 __device__ __forceinline__ float act_lo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float act_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 __device__ __forceinline__ float4 act_unpack4(uint2 h) { return make_float4(act_lo(h.x), act_hi(h.x), act_lo(h.y), act_hi(h.y)); }
@@ -34,7 +35,7 @@ __device__ __forceinline__ float act_ld1(const void* base, long off) {
 }
 template <bool BF>
 __device__ __forceinline__ void act_st1(void* base, long off, float v) {
-    if (BF) reinterpret_cast<unsigned short*>(base)[off] = (unsigned short)(act_pack2(v, 0.f) & 0xffffu);
+    if (BF) reinterpret_cast<unsigned short*>(base)[off] = act_bf16_1(v);
     else reinterpret_cast<float*>(base)[off] = v;
 }
 // runtime-flag forms

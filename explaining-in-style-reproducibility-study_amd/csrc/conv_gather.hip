@@ -23,14 +23,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 constexpr int GBM = 128, GBN = 128;
 constexpr int RING = 4;
@@ -47,13 +45,6 @@ struct GatherParams {
     int M, stages, ksplit, stages_per_split;
 };
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned short f2bf_rne(float f) {  // v_cvt_pk_bf16_f32, as the split-K epilogue rounds
-    f32x2_t v = {f, 0.f};
-    bf16x2_t r = __builtin_convertvector(v, bf16x2_t);
-    return (unsigned short)(*reinterpret_cast<unsigned*>(&r) & 0xffffu);
-}
 
 // ---- WHOLE-LINE staging on 8 waves (round 5).  The round-2 kernel (deleted in round 6; git history, profiles/design_history_r1_r4.md)
 // staged 16-channel groups: every DMA instruction fetched 32 bytes from each of 32 rows, a request shape the vector-memory path serves at 15-17 B/clk/CU whatever
@@ -241,7 +232,7 @@ __global__ __launch_bounds__(512, 1) void conv_gather_line_kernel(GatherParams p
                 const int qh = qq / p.Ws, qw = qq - qh * p.Ws;
                 mm = (bb * p.H + 2 * qh + py) * p.W + 2 * qw + px;
             }
-            if (ok && p.y) p.y[(long)mm * p.N + n] = f2bf_rne(acc[j][r]);
+            if (ok && p.y) p.y[(long)mm * p.N + n] = act_bf16_1(acc[j][r]);  // RNE, as the split-K epilogue rounds
             else if (ok) out[(long)mm * p.N + n] = acc[j][r];
         }
     }
@@ -304,15 +295,11 @@ int stylex_launch_gather(ConvKParams& p, void* workspace, int64_t workspace_byte
     gather_plan(p, &ks, &per);
     if (workspace_bytes < (int64_t)ks * p.M * p.N * (int64_t)sizeof(float)) return STYLEX_NOT_APPLICABLE;
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return STYLEX_NOT_APPLICABLE;
-    // 0 = not asked yet, 1 = granted, -1 = refused (a device with less LDS): the generic kernel behind this one serves the launch
-    static int attr_state = 0;
-    if (attr_state == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gather_line_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, RING * LSTAGE);
-        attr_state = e == hipSuccess ? 1 : -1;
-        if (e != hipSuccess) (void)hipGetLastError();
+    // refused (a device with less LDS): the generic kernel behind this one serves the launch
+    if (stylex_dynamic_lds_once<conv_gather_line_kernel>(RING * LSTAGE) != hipSuccess) {
+        (void)hipGetLastError();
+        return STYLEX_NOT_APPLICABLE;
     }
-    if (attr_state < 0) return STYLEX_NOT_APPLICABLE;
     GatherParams g;
     g.x = reinterpret_cast<const unsigned short*>(p.a);
     g.w = reinterpret_cast<const unsigned short*>(p.w);

@@ -17,20 +17,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    f32x2_t v = {lo, hi};
-    bf16x2_t r = __builtin_convertvector(v, bf16x2_t);  // v_cvt_pk_bf16_f32 (RNE)
-    return *reinterpret_cast<unsigned*>(&r);
-}
 
 constexpr int ROWB = 80;  // LDS row pitch in bytes (32 bf16 + 16 B pad)
 
@@ -140,14 +132,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_bf16_kernel(ConvKParams p
                                          __float_as_uint(hreg[it].z), __float_as_uint(hreg[it].w));
                     if (p.a_scale) {
                         float4 f0 = act_unpack4(make_uint2(v.x, v.y)), f1 = act_unpack4(make_uint2(v.z, v.w));
-                        v.x = pack_bf16(f0.x * sc.x, f0.y * sc.y); v.y = pack_bf16(f0.z * sc.z, f0.w * sc.w);
-                        v.z = pack_bf16(f1.x * sc2.x, f1.y * sc2.y); v.w = pack_bf16(f1.z * sc2.z, f1.w * sc2.w);
+                        v.x = act_pack2(f0.x * sc.x, f0.y * sc.y); v.y = act_pack2(f0.z * sc.z, f0.w * sc.w);
+                        v.z = act_pack2(f1.x * sc2.x, f1.y * sc2.y); v.w = act_pack2(f1.z * sc2.z, f1.w * sc2.w);
                     }
                     *reinterpret_cast<uint4*>(smem + hp * ROWB + q8 * 16) = v;
                 } else {
                     uint2 v;
-                    v.x = pack_bf16(hreg[it].x * sc.x, hreg[it].y * sc.y);
-                    v.y = pack_bf16(hreg[it].z * sc.z, hreg[it].w * sc.w);
+                    v.x = act_pack2(hreg[it].x * sc.x, hreg[it].y * sc.y);
+                    v.y = act_pack2(hreg[it].z * sc.z, hreg[it].w * sc.w);
                     *reinterpret_cast<uint2*>(smem + hp * ROWB + q8 * 8) = v;
                 }
             }
@@ -288,8 +280,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_bf16_kernel(ConvKParams p
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : slope * v[e];
                     }
-                    P[g][0] = pack_bf16(v[0], v[1]);
-                    P[g][1] = pack_bf16(v[2], v[3]);
+                    P[g][0] = act_pack2(v[0], v[1]);
+                    P[g][1] = act_pack2(v[2], v[3]);
                 }
                 if (w8) {
 #pragma unroll
@@ -372,7 +364,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_bf16_kernel(ConvKParams p
                     }
                     if (p.flags & (STYLEX_EPI_LRELU | STYLEX_EPI_RELU)) v = v > 0.f ? v : ((p.flags & STYLEX_EPI_RELU) ? 0.f : 0.2f * v);
                     char* d = smem + pix * OROW + (j * 32 + lj) * OUT_ES;
-                    if (ABF) *reinterpret_cast<unsigned short*>(d) = (unsigned short)(pack_bf16(v, 0.f) & 0xffffu);
+                    if (ABF) *reinterpret_cast<unsigned short*>(d) = act_bf16_1(v);
                     else *reinterpret_cast<float*>(d) = v;
                 }
             }
@@ -433,12 +425,8 @@ int launch_halo(const ConvKParams& p, hipStream_t s) {
     constexpr int TH = 256 / TW, NP = (TH + 2) * (TW + 2), BN = TN * 32;
     constexpr size_t sm = (size_t)NP * ROWB + 9 * ((size_t)BN * ROWB + 64);
     auto k = conv3x3_halo_bf16_kernel<TW, TN, ABF, S2D, EPIX>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    const hipError_t e = stylex_dynamic_lds_once<conv3x3_halo_bf16_kernel<TW, TN, ABF, S2D, EPIX>>((int)sm);
+    if (e != hipSuccess) return (int)e;
     long tiles = (long)p.B * ((p.Wo + TW - 1) / TW) * ((p.Ho + TH - 1) / TH);
     long blocks = tiles * ((p.N + BN - 1) / BN);
     stylex_note_kernel("conv3x3_halo_bf16_kernel<%d, %d, %s, %s, %s>", TW, TN, ABF ? "true" : "false", S2D ? "true" : "false",

@@ -22,12 +22,9 @@
 
 #include <type_traits>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 // Epilogue without LDS: the MFMA operands are swapped (D^T = W x X^T), so a lane's accumulators are 4 CONSECUTIVE
 // CHANNELS of one pixel; one v_permlane32_swap per dword pairs the two half-waves' quads into 8 consecutive channels and
@@ -37,14 +34,8 @@ namespace {
 
 __device__ uint4 g_zero_page_fwd[4];
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef __attribute__((address_space(1))) const void* gl_void_ptr;
 
-__device__ __forceinline__ unsigned short to_bf16(float v) {
-    f32x2_t t = {v, 0.f};
-    bf16x2_t r = __builtin_convertvector(t, bf16x2_t);
-    return (unsigned short)(*reinterpret_cast<unsigned*>(&r) & 0xffffu);
-}
 
 constexpr int TW = 32, TH = 16, HWD = TW + 2, NP = (TH + 2) * HWD;  // 612 halo pixels
 constexpr int ROW = 32;                                              // bytes per LDS row (16 bf16)
@@ -309,12 +300,12 @@ __global__ __launch_bounds__(256, TNJ == 4 ? 1 : 2) void conv3x3_halo_dma_kernel
     unsigned char* mask_out = S2D ? nullptr : p.mask;          // STYLEX_EPI_MASK_OUT
     auto gatem = [&](unsigned u, unsigned bits) -> unsigned {  // two bf16 of dx, gate bits (element > 0) in bits 0 and 1
         const float a0 = __uint_as_float(u << 16), c0 = __uint_as_float(u & 0xffff0000u);
-        return (unsigned)to_bf16((bits & 1u) ? a0 : gslope * a0) | ((unsigned)to_bf16((bits & 2u) ? c0 : gslope * c0) << 16);
+        return (unsigned)act_bf16_1((bits & 1u) ? a0 : gslope * a0) | ((unsigned)act_bf16_1((bits & 2u) ? c0 : gslope * c0) << 16);
     };
     auto gate2 = [&](unsigned u, unsigned g) -> unsigned {  // two bf16 of dx times the LeakyReLU derivative at the gate
         const float a0 = __uint_as_float(u << 16), c0 = __uint_as_float(u & 0xffff0000u);
         const float ga = __uint_as_float(g << 16), gc = __uint_as_float(g & 0xffff0000u);
-        return (unsigned)to_bf16(ga > 0.f ? a0 : gslope * a0) | ((unsigned)to_bf16(gc > 0.f ? c0 : gslope * c0) << 16);
+        return (unsigned)act_bf16_1(ga > 0.f ? a0 : gslope * a0) | ((unsigned)act_bf16_1(gc > 0.f ? c0 : gslope * c0) << 16);
     };
     {
         // block merge of DiscriminatorBlock (:743) on the space-to-depth forward: (conv + bias + residual) * res_scale in fp32
@@ -363,8 +354,8 @@ __global__ __launch_bounds__(256, TNJ == 4 ? 1 : 2) void conv3x3_halo_dma_kernel
                         v2 = v2 > 0.f ? v2 : slope * v2;
                         v3 = v3 > 0.f ? v3 : slope * v3;
                     }
-                    P[g][0] = (unsigned)to_bf16(v0) | ((unsigned)to_bf16(v1) << 16);
-                    P[g][1] = (unsigned)to_bf16(v2) | ((unsigned)to_bf16(v3) << 16);
+                    P[g][0] = (unsigned)act_bf16_1(v0) | ((unsigned)act_bf16_1(v1) << 16);
+                    P[g][1] = (unsigned)act_bf16_1(v2) | ((unsigned)act_bf16_1(v3) << 16);
                 }
                 // upper half-wave's quad g <-> lower half-wave's quad g+1 (g = 0, 2): afterwards the lower lanes hold channels
                 // 8g .. 8g+7 for g = 0, 2 and the upper lanes for g = 1, 3
@@ -411,13 +402,8 @@ __global__ __launch_bounds__(256, TNJ == 4 ? 1 : 2) void conv3x3_halo_dma_kernel
 // output width that is a multiple of 64 (64-channel tiles) or >= 128 with >= 128 input channels (128-channel tiles).
 template <int TNJ, bool S2D = false>
 static int launch_dma(const ConvKParams& p, hipStream_t s) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_dma_kernel<TNJ, S2D>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, DmaCfg<TNJ>::SMEM_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    const hipError_t e = stylex_dynamic_lds_once<conv3x3_halo_dma_kernel<TNJ, S2D>>(DmaCfg<TNJ>::SMEM_BYTES);
+    if (e != hipSuccess) return (int)e;
     long tiles = (long)p.B * ((p.Wo + TW - 1) / TW) * ((p.Ho + TH - 1) / TH);
     long blocks = tiles * ((p.N + DmaCfg<TNJ>::BN - 1) / DmaCfg<TNJ>::BN);
     stylex_note_kernel("conv3x3_halo_dma_kernel<%d, %s>", TNJ, S2D ? "true" : "false");

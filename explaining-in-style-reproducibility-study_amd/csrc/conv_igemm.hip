@@ -30,23 +30,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
 constexpr int BK = 32;  // K-tile depth (fp32 elements)
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    f32x2_t v = {lo, hi};
-    bf16x2_t r = __builtin_convertvector(v, bf16x2_t);  // v_cvt_pk_bf16_f32, round-to-nearest-even
-    return *reinterpret_cast<unsigned*>(&r);
-}
-__device__ __forceinline__ unsigned short f2bf(float f) { return (unsigned short)(pack_bf16(f, 0.f) & 0xffffu); }
 
 // ------------------------------------------------------------------------------------------
 // Row descriptor: which gathered source rows (pixels) a thread stages.
@@ -267,7 +258,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvKParams p) {
                     }
                 }
                 if (BF16)  // same packed form as the vector path
-                    rb[j] = make_float4(__uint_as_float(pack_bf16(v[0], v[1])), __uint_as_float(pack_bf16(v[2], v[3])), 0.f, 0.f);
+                    rb[j] = make_float4(__uint_as_float(act_pack2(v[0], v[1])), __uint_as_float(act_pack2(v[2], v[3])), 0.f, 0.f);
                 else
                     rb[j] = make_float4(v[0], v[1], v[2], v[3]);
             }
@@ -287,8 +278,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvKParams p) {
                         const float* sp = p.a_scale + (long)rows[j].b * p.Ck + c0;
                         float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
                         float4 f0 = act_unpack4(make_uint2(v.x, v.y)), f1 = act_unpack4(make_uint2(v.z, v.w));
-                        v.x = pack_bf16(f0.x * s0.x, f0.y * s0.y); v.y = pack_bf16(f0.z * s0.z, f0.w * s0.w);
-                        v.z = pack_bf16(f1.x * s1.x, f1.y * s1.y); v.w = pack_bf16(f1.z * s1.z, f1.w * s1.w);
+                        v.x = act_pack2(f0.x * s0.x, f0.y * s0.y); v.y = act_pack2(f0.z * s0.z, f0.w * s0.w);
+                        v.z = act_pack2(f1.x * s1.x, f1.y * s1.y); v.w = act_pack2(f1.z * s1.z, f1.w * s1.w);
                     }
                 }
                 *reinterpret_cast<uint4*>(a + (r0 + RPP * j) * LDH + kq * 8) = v;
@@ -304,8 +295,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvKParams p) {
 #pragma unroll
             for (int j = 0; j < RA; ++j) {
                 uint2 v;
-                v.x = pack_bf16(ra[j].x, ra[j].y);
-                v.y = pack_bf16(ra[j].z, ra[j].w);
+                v.x = act_pack2(ra[j].x, ra[j].y);
+                v.y = act_pack2(ra[j].z, ra[j].w);
                 *reinterpret_cast<uint2*>(a + (r0 + RPP * j) * LDH + kq * 4) = v;
             }
 #pragma unroll
@@ -578,19 +569,19 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvKParams p) {
             for (int j = 0; j < A_PER; ++j) {
                 int idx = tid + 256 * j;
                 int pr = idx / A_V, q = idx % A_V;
-                a[(q * 4 + 0) * LDHA + pr] = f2bf(ra[j].x);
-                a[(q * 4 + 1) * LDHA + pr] = f2bf(ra[j].y);
-                a[(q * 4 + 2) * LDHA + pr] = f2bf(ra[j].z);
-                a[(q * 4 + 3) * LDHA + pr] = f2bf(ra[j].w);
+                a[(q * 4 + 0) * LDHA + pr] = act_bf16_1(ra[j].x);
+                a[(q * 4 + 1) * LDHA + pr] = act_bf16_1(ra[j].y);
+                a[(q * 4 + 2) * LDHA + pr] = act_bf16_1(ra[j].z);
+                a[(q * 4 + 3) * LDHA + pr] = act_bf16_1(ra[j].w);
             }
 #pragma unroll
             for (int j = 0; j < B_PER; ++j) {
                 int idx = tid + 256 * j;
                 int pr = idx / B_V, q = idx % B_V;
-                b[(q * 4 + 0) * LDHB + pr] = f2bf(rb[j].x);
-                b[(q * 4 + 1) * LDHB + pr] = f2bf(rb[j].y);
-                b[(q * 4 + 2) * LDHB + pr] = f2bf(rb[j].z);
-                b[(q * 4 + 3) * LDHB + pr] = f2bf(rb[j].w);
+                b[(q * 4 + 0) * LDHB + pr] = act_bf16_1(rb[j].x);
+                b[(q * 4 + 1) * LDHB + pr] = act_bf16_1(rb[j].y);
+                b[(q * 4 + 2) * LDHB + pr] = act_bf16_1(rb[j].z);
+                b[(q * 4 + 3) * LDHB + pr] = act_bf16_1(rb[j].w);
             }
         } else {
 #pragma unroll
@@ -867,7 +858,7 @@ __device__ __forceinline__ OUT cvt_out(float v);
 template <>
 __device__ __forceinline__ float cvt_out<float>(float v) { return v; }
 template <>
-__device__ __forceinline__ unsigned short cvt_out<unsigned short>(float v) { return f2bf(v); }
+__device__ __forceinline__ unsigned short cvt_out<unsigned short>(float v) { return act_bf16_1(v); }
 
 template <typename OUT>
 __global__ void pack_weight_kernel(const float* __restrict__ w, OUT* __restrict__ wf, OUT* __restrict__ wb, int N,
@@ -924,8 +915,8 @@ __global__ void splitk_epilogue_kernel(ConvKParams p) {
             for (int e = 0; e < 4; ++e) r[e] = splitk_finish(p, r[e], (long)o + e, n + e, b, oh, ow);
             if (p.act_bf16) {
                 uint2 h;
-                h.x = pack_bf16(r[0], r[1]);
-                h.y = pack_bf16(r[2], r[3]);
+                h.x = act_pack2(r[0], r[1]);
+                h.y = act_pack2(r[2], r[3]);
                 *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.y) + o) = h;
             } else {
                 *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + o) = make_float4(r[0], r[1], r[2], r[3]);
@@ -965,7 +956,7 @@ __global__ void pack_weight_s2d_kernel(const float* __restrict__ w, unsigned sho
             int kh = kh2 == 0 ? 0 : 1 + sy, kw = kw2 == 0 ? 0 : 1 + sx;
             v = w[((long)n * C + c) * 9 + kh * 3 + kw];
         }
-        unsigned short h = f2bf(v);
+        unsigned short h = act_bf16_1(v);
         if (wf) wf[((long)n * 9 + t2) * C4 + sc] = h;
         if (wb) wb[((long)sc * 9 + t2) * N + n] = h;
     }
@@ -1001,12 +992,8 @@ int launch_igemm(const ConvKParams& p, hipStream_t s) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     auto k = conv_igemm_kernel<WM, WN, TM, TN, VEC4, BF16, BKT, ABF>;
     constexpr size_t sm = igemm_smem<WM, WN, TM, TN, VEC4, BF16, BKT>();
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    const hipError_t e = stylex_dynamic_lds_once<conv_igemm_kernel<WM, WN, TM, TN, VEC4, BF16, BKT, ABF>>((int)sm);
+    if (e != hipSuccess) return (int)e;
     long blocks = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     stylex_note_kernel("conv_igemm_kernel<%d, %d, %d, %d, %s, %s, %d, %s>", WM, WN, TM, TN, VEC4 ? "true" : "false",
                        BF16 ? "true" : "false", BKT, ABF ? "true" : "false");
@@ -1038,12 +1025,8 @@ template <int TN_, int TC_, bool VEC4, bool BF16>
 int launch_wgrad(const ConvKParams& p, int blocks, hipStream_t s) {
     auto k = conv_wgrad_kernel<TN_, TC_, VEC4, BF16>;
     constexpr size_t sm = wgrad_smem<TN_, TC_, BF16>();
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    const hipError_t e = stylex_dynamic_lds_once<conv_wgrad_kernel<TN_, TC_, VEC4, BF16>>((int)sm);
+    if (e != hipSuccess) return (int)e;
     stylex_note_kernel("conv_wgrad_kernel<%d, %d, %s, %s>", TN_, TC_, VEC4 ? "true" : "false", BF16 ? "true" : "false");
     hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), sm, s, p);
     return (int)hipGetLastError();

@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
 // cache policy of the output stores (buffer_store aux bits; 2 = nt, streaming: tools/bench_s2d_dgrad.py A/B, DESIGN §3 "Round 5")
@@ -30,11 +31,6 @@
 #define LN_STORE_AUX 0
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct StylexLineArgs {
     int total_tiles;
@@ -43,7 +39,6 @@ struct StylexLineArgs {
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 constexpr int TH = 8, TW = 32, HWD = TW + 2, NP = (TH + 2) * HWD;  // 340 halo pixels
 constexpr int H_PIECES = (NP + 7) / 8;                               // 43 DMA pieces of 8 pixels (1 KiB)
@@ -55,10 +50,6 @@ constexpr int SMEM = DUMP_BASE + 1024;                               // 162816 b
 constexpr int HP = (H_PIECES + 7) / 8;                               // 6 halo pieces per wave and tile (waves 3-7: one dummy)
 constexpr unsigned OOB = 0x80000000u;
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* smem, int lds_off, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)(smem + lds_off), 16, voff, 0, 0, 0);
-}
-__device__ __forceinline__ int fastdiv(int n, unsigned magic) { return magic ? (int)__umulhi((unsigned)n, magic) : n; }
 
 template <int EPI>
 __global__ __launch_bounds__(512) void conv3x3_line64_kernel(ConvKParams p, StylexLineArgs la) {
@@ -69,11 +60,10 @@ __global__ __launch_bounds__(512) void conv3x3_line64_kernel(ConvKParams p, Styl
     const int tiles_x = W >> 5, tiles_y = H >> 3, tpi = tiles_x * tiles_y;
 
     // static tile list, XCD-contiguous (as conv_pipe.hip)
-    const int xcd = blockIdx.x & 7, bslot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-    const int tq = la.total_tiles >> 3, tr = la.total_tiles & 7;
-    const int xs = xcd * tq + (xcd < tr ? xcd : tr), xn = tq + (xcd < tr ? 1 : 0);
+    int xs, xn, bslot, nslots;
+    xcd_tile_span(la.total_tiles, xs, xn, bslot, nslots);
     if (bslot >= xn) return;
-    const int my_tiles = (xn - bslot + nslots - 1) / nslots;
+    const int my_tiles = xcd_my_tiles(xn, bslot, nslots);
     auto decode = [&](int k, int& b, int& y0, int& x0) {
         int pt = xs + bslot + k * nslots;
         b = fastdiv(pt, la.m_tpi);
@@ -267,27 +257,14 @@ __global__ __launch_bounds__(512) void conv3x3_line64_kernel(ConvKParams p, Styl
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // dump-row DMAs must not outlive the block's LDS allocation
 }
 
-int g_line_cus = 0;
-unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
 
 template <int EPI>
 int launch_line(const ConvKParams& p, hipStream_t s) {
-    // 0 = not asked yet, 1 = granted, -1 = refused (a device with less than 160 KiB of LDS): the pipelined and per-tile
-    // kernels behind this one in stylex_launch_halo's dispatch then serve the launch
-    static int attr_state = 0;
-    if (attr_state == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_line64_kernel<EPI>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        attr_state = e == hipSuccess ? 1 : -1;
-        if (e != hipSuccess) (void)hipGetLastError();
-    }
-    if (attr_state < 0) return STYLEX_NOT_APPLICABLE;
-    if (!g_line_cus) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        g_line_cus = n > 0 ? (n & ~7) : 256;
-        if (g_line_cus < 8) g_line_cus = 8;
+    // refused (a device with less than 160 KiB of LDS): the pipelined and per-tile kernels behind this one in
+    // stylex_launch_halo's dispatch then serve the launch
+    if (stylex_dynamic_lds_once<conv3x3_line64_kernel<EPI>>(SMEM) != hipSuccess) {
+        (void)hipGetLastError();
+        return STYLEX_NOT_APPLICABLE;
     }
     const int tiles_x = p.Wo / TW, tiles_y = p.Ho / TH;
     StylexLineArgs la;
@@ -295,7 +272,7 @@ int launch_line(const ConvKParams& p, hipStream_t s) {
     la.m_tpi = magic_of(tiles_x * tiles_y);
     la.m_tx = magic_of(tiles_x);
     stylex_note_kernel("conv3x3_line64_kernel<%d>", EPI);
-    hipLaunchKernelGGL((conv3x3_line64_kernel<EPI>), dim3((unsigned)g_line_cus), dim3(512), SMEM, s, p, la);
+    hipLaunchKernelGGL((conv3x3_line64_kernel<EPI>), dim3((unsigned)stylex_cu_count()), dim3(512), SMEM, s, p, la);
     return (int)hipGetLastError();
 }
 

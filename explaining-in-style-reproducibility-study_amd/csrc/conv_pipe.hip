@@ -26,18 +26,13 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
 // cache policy of the output stores (buffer_store aux bits; 2 = nt, streaming: tools/bench_s2d_dgrad.py A/B, DESIGN §3 "Round 5")
 #ifndef PIPE_STORE_AUX
 #define PIPE_STORE_AUX 0
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // kernel argument (not in the anonymous namespace: a kernel's host stub needs externally visible parameter types)
 struct StylexPipeArgs {
@@ -58,13 +53,6 @@ struct StylexPipeArgs {
 namespace {
 
 typedef StylexPipeArgs PipeArgs;
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-
-__device__ __forceinline__ unsigned short to_bf16(float v) {
-    f32x2_t t = {v, 0.f};
-    bf16x2_t r = __builtin_convertvector(t, bf16x2_t);
-    return (unsigned short)(*reinterpret_cast<unsigned*>(&r) & 0xffffu);
-}
 
 // NT = output channels per block tile.  128: 16x32 px tile, waves = 4 row groups x 2 channel halves;
 // 64: 32x32 px tile, waves = 8 row groups.  Every wave owns 4 pixel rows (4 MFMA row tiles of 32 px) x 64 channels.
@@ -86,24 +74,7 @@ struct PipeCfg {
     static constexpr int RG = TH / 4;                                  // row groups: 4 / 8
 };
 
-// one LDS-DMA piece: 64 lanes x 16 bytes -> LDS [lds_off, lds_off + 1 KiB) (wave-uniform), source = buffer base +
-// per-lane voff + wave-uniform soff; lanes whose voff is out of range write zeros
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* smem, int lds_off, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)(smem + lds_off), 16, voff, soff, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// LDS operand reads as inline asm: hipcc sinks every compiler-visible ds_read to just before its MFMA and waits
-// lgkmcnt(0) there (no software pipelining across taps); the asm forms pin the issue point, and the wait statement
-// names every destination "+v" so that no consumer (and no register copy) is scheduled above it.
-template <int OFF>
-__device__ __forceinline__ void lds_read16(bf16x8& dst, int addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
+// (dma16, wait_vmcnt, lds_read16, mfma1, fastdiv: conv_prims.h, with the reasons why the reads and MFMAs are asm)
 __device__ __forceinline__ void lds_wait(bf16x8 (&av)[4], bf16x8 (&bv)[2]) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(av[0]), "+v"(av[1]), "+v"(av[2]), "+v"(av[3]), "+v"(bv[0]), "+v"(bv[1]));
 }
@@ -126,24 +97,12 @@ __device__ __forceinline__ void load_tap(bf16x8 (&av)[4], bf16x8 (&bv)[2], const
     for (int i = 0; i < 4; ++i) lds_read16<0>(av[i], addr[i]);
 }
 
-// MFMAs as inline asm too: the builtin is a pure value operation that instruction selection may place anywhere between
-// its operands' definitions and its result's use — hipcc sank MFMAs across two and three taps, keeping their operands
-// alive (36-42 spilled registers inside the loop).  asm volatile statements keep their program order.
-// Hazards the compiler cannot see: a VALU read of an accumulator needs 12 wait states after the MFMA that wrote it
-// (the epilogue is preceded by explicit s_nops); accumulate chains (D as the next C) need none.
-__device__ __forceinline__ void mfma1(f32x16& acc, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
 __device__ __forceinline__ void mfma8(f32x16 (&acc)[4][2], const bf16x8 (&av)[4], const bf16x8 (&bv)[2]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) mfma1(acc[i][j], bv[j], av[i]);  // D^T = W x X^T: rows = channels
 }
-
-// q = n / d for n * d < 2^32 with the host-computed M = ceil(2^32 / d) (tile indices: a few thousand)
-__device__ __forceinline__ int fastdiv(int n, unsigned magic) { return magic ? (int)__umulhi((unsigned)n, magic) : n; }  // magic 0: d = 1
-
 
 // EPI: 0 = bias / activation / mask-out epilogue, 1 = data gradient gated by an activation tensor, 2 = by a bit mask
 template <int NT, int EPI>
@@ -163,14 +122,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(ConvKParams p, Pip
 
     // ---- static tile list: XCD x (blocks x, x+8, ...) owns a contiguous range, its blocks interleave inside it, so the
     // 32 CUs of an XCD work on 32 consecutive tiles (channel tiles of one pixel tile, then the neighbouring pixel tiles)
-    const int xcd = blockIdx.x & 7, bslot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-    const int tq = pa.total_tiles >> 3, tr = pa.total_tiles & 7;
-    const int xs = xcd * tq + (xcd < tr ? xcd : tr), xn = tq + (xcd < tr ? 1 : 0);
+    int xs, xn, bslot, nslots;
+    xcd_tile_span(pa.total_tiles, xs, xn, bslot, nslots);
     if (bslot >= xn) return;
     // de-phase the CUs (experiment, dbg >> 8 = units of ~0.5 us): all blocks start together and every tile takes the same
     // time, so without it all 256 CUs issue their 128 KiB of output stores in the same microsecond
     for (int i = (bslot & 3) * (PIPE_DBG >> 8); i > 0; --i) __builtin_amdgcn_s_sleep(16);
-    const int my_tiles = (xn - bslot + nslots - 1) / nslots;
+    const int my_tiles = xcd_my_tiles(xn, bslot, nslots);
     const int nchunks = C >> 4;
     const int total = my_tiles * nchunks;
 
@@ -543,27 +501,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_kernel(ConvKParams p, Pip
     wait_vmcnt<0>();  // dump-row DMAs of the stream's tail must not outlive the block's LDS allocation
 }
 
-int g_num_cus = 0;
-
-unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
-
 template <int NT, int EPI>
 int launch_pipe(const ConvKParams& p, hipStream_t s) {
     using Cfg = PipeCfg<NT>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_pipe_kernel<NT, EPI>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    if (!g_num_cus) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        g_num_cus = n > 0 ? (n & ~7) : 256;
-        if (g_num_cus < 8) g_num_cus = 8;
-    }
+    const hipError_t e = stylex_dynamic_lds_once<conv3x3_pipe_kernel<NT, EPI>>(Cfg::SMEM);
+    if (e != hipSuccess) return (int)e;
     const int tiles_x = (p.Wo + 31) / 32, tiles_y = (p.Ho + Cfg::TH - 1) / Cfg::TH, n_tiles = p.N / NT;
     PipeArgs pa;
     pa.total_tiles = p.B * tiles_x * tiles_y * n_tiles;
@@ -576,7 +518,7 @@ int launch_pipe(const ConvKParams& p, hipStream_t s) {
     pa.dbg = 0;
 #endif
     stylex_note_kernel("conv3x3_pipe_kernel<%d, %d>", NT, EPI);
-    hipLaunchKernelGGL((conv3x3_pipe_kernel<NT, EPI>), dim3((unsigned)g_num_cus), dim3(512), Cfg::SMEM, s, p, pa);
+    hipLaunchKernelGGL((conv3x3_pipe_kernel<NT, EPI>), dim3((unsigned)stylex_cu_count()), dim3(512), Cfg::SMEM, s, p, pa);
     return (int)hipGetLastError();
 }
 

@@ -11,20 +11,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 
-__device__ __forceinline__ unsigned short to_bf16(float v) {
-    f32x2_t t = {v, 0.f};
-    bf16x2_t r = __builtin_convertvector(t, bf16x2_t);
-    return (unsigned short)(*reinterpret_cast<unsigned*>(&r) & 0xffffu);
-}
 
 constexpr int TW = 32, TH = 8, HWD = TW + 2, NP = (TH + 2) * HWD;  // 340 halo pixels of 16 bytes
 constexpr int KSTEPS = 5;                                            // 10 tap slots of 8 channels (tap 9 = zeros)
@@ -111,7 +103,7 @@ __global__ __launch_bounds__(256) void conv3x3_rgb_kernel(ConvKParams p) {
                 const int px = (r & 3) + 8 * (r >> 2) + 4 * lk;
                 float v = acc[i][j][r] + bias[j];
                 if (act) v = v > 0.f ? v : 0.2f * v;
-                *reinterpret_cast<unsigned short*>(scr + px * 128 + (j * 32 + li) * 2) = to_bf16(v);
+                *reinterpret_cast<unsigned short*>(scr + px * 128 + (j * 32 + li) * 2) = act_bf16_1(v);
             }
         const int y = y0 + 2 * wave + i;
 #pragma unroll

@@ -30,6 +30,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
 // cache policy of the output stores (buffer_store aux bits; 2 = nt, streaming: tools/bench_s2d_dgrad.py A/B, DESIGN §3 "Round 5")
@@ -37,11 +38,6 @@
 #define SD_STORE_AUX 0
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct StylexS2dDgradArgs {
     int total_tiles;           // B * tiles_y * tiles_x * c_groups
@@ -51,7 +47,6 @@ struct StylexS2dDgradArgs {
 namespace {
 
 typedef StylexS2dDgradArgs SdArgs;
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 // block = NW waves: 8 (a 64-channel group in four sub-positions = 256 output channels, one block per CU) or 4 (a 32-channel
 // group = 128 output channels, two blocks per CU); pixel tile 8 x 32 or 16 x 16 (TW = 16: images 16 pixels wide)
@@ -76,18 +71,7 @@ constexpr bool SD_NO_HALO = false;
 #endif
 constexpr bool SD_EARLY = SD_EARLY_ISSUE != 0;  // 1: the whole DMA of the next stage goes out behind the first MFMAs of a stage
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* smem, int lds_off, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)(smem + lds_off), 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ int fastdiv(int n, unsigned magic) { return magic ? (int)__umulhi((unsigned)n, magic) : n; }
 
-template <int OFF>
-__device__ __forceinline__ void lds_read16(bf16x8& dst, int addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-__device__ __forceinline__ void mfma1(f32x16& acc, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
 
 // (sub-position, tap) slots of the staged weights, in LDS order: slot j holds rows [64 j, 64 j + 64)
 //   j:    0     1     2     3     4     5     6     7     8
@@ -154,9 +138,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_s2d_dgrad_kernel(ConvKParams 
     const int nch = NI >> 5;                                 // 32-channel K stages per tile
 
     // static tile list, XCD-contiguous (conv_pipe.hip): the channel groups of one pixel tile are neighbours
-    const int xcd = blockIdx.x & 7, bslot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-    const int tq = sa.total_tiles >> 3, tr = sa.total_tiles & 7;
-    const int xs = xcd * tq + (xcd < tr ? xcd : tr), xn = tq + (xcd < tr ? 1 : 0);
+    int xs, xn, bslot, nslots;
+    xcd_tile_span(sa.total_tiles, xs, xn, bslot, nslots);
     if (bslot >= xn) return;
 #ifdef SD_STAGGER
     // second residents of a CU (the upper half of the grid) start about half a tile late, so that the two blocks of a CU are
@@ -164,7 +147,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_s2d_dgrad_kernel(ConvKParams 
     if (NW == 4 && bslot >= (nslots >> 1))
         for (int i = 0; i < SD_STAGGER * (nch + 2); ++i) __builtin_amdgcn_s_sleep(16);  // 16 x 64 clocks
 #endif
-    const int my_tiles = (xn - bslot + nslots - 1) / nslots;
+    const int my_tiles = (xn - bslot + nslots - 1) / nslots;  // xcd_my_tiles() spelled out: the call changes this kernel's code
     const int total = my_tiles * nch;
     auto decode = [&](int k, int& b, int& y0, int& x0, int& c0) {
         const int t = xs + bslot + k * nslots;
@@ -404,26 +387,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_s2d_dgrad_kernel(ConvKParams 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tail DMAs must not outlive the block's LDS allocation
 }
 
-int g_sd_cus = 0;
-unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
 
 template <int TW, int NW>
 int launch_sd(const ConvKParams& p, hipStream_t s) {
     using Cfg = SdCfg<TW, NW>;
-    static int attr_state = 0;
-    if (attr_state == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_s2d_dgrad_kernel<TW, NW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-        attr_state = e == hipSuccess ? 1 : -1;
-    }
-    if (attr_state < 0) return STYLEX_NOT_APPLICABLE;
-    if (!g_sd_cus) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        g_sd_cus = n > 0 ? (n & ~7) : 256;
-        if (g_sd_cus < 8) g_sd_cus = 8;
-    }
+    if (stylex_dynamic_lds_once<conv_s2d_dgrad_kernel<TW, NW>>(Cfg::SMEM) != hipSuccess) return STYLEX_NOT_APPLICABLE;
     const int tiles_x = p.Wo / TW, tiles_y = p.Ho / Cfg::TH, cgs = p.s2d_c / Cfg::CG;
     SdArgs sa;
     sa.total_tiles = p.B * tiles_x * tiles_y * cgs;
@@ -431,7 +399,7 @@ int launch_sd(const ConvKParams& p, hipStream_t s) {
     sa.m_tpi = magic_of(tiles_x * tiles_y);
     sa.m_tx = magic_of(tiles_x);
     stylex_note_kernel("conv_s2d_dgrad_kernel<%d, %d>", TW, NW);
-    const int blocks = NW == 4 ? 2 * g_sd_cus : g_sd_cus;  // 4-wave blocks: two per CU
+    const int blocks = NW == 4 ? 2 * stylex_cu_count() : stylex_cu_count();  // 4-wave blocks: two per CU
     hipLaunchKernelGGL((conv_s2d_dgrad_kernel<TW, NW>), dim3((unsigned)blocks), dim3(NW * 64), Cfg::SMEM, s, p, sa);
     return (int)hipGetLastError();
 }

@@ -29,6 +29,7 @@
 
 #include <type_traits>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
 // cache policy of the output stores (buffer_store aux bits; 2 = nt, streaming: tools/bench_s2d_dgrad.py A/B, DESIGN §3 "Round 5")
@@ -36,11 +37,6 @@
 #define SF_STORE_AUX 0
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct StylexS2dFwdArgs {
     int total_tiles;             // B * tiles_y * tiles_x * n_groups
@@ -50,7 +46,6 @@ struct StylexS2dFwdArgs {
 namespace {
 
 typedef StylexS2dFwdArgs SfArgs;
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 constexpr unsigned OOB = 0x80000000u;
 
 // block tile: NW waves x 2 NF accumulator tiles = PXF 32-pixel fragments x NT output channels; TW = tile width in pixels.
@@ -96,18 +91,7 @@ typedef Phase<2, 0, -1, 0, 0> PhLeft;      // sub-position 1 (taps 3, 4) and the
 typedef Phase<2, -1, 0, 0, 0> PhUp;        // sub-position 2 (taps 1, 4)
 typedef Phase<2, -1, -1, -1, 0> PhUpLeft;  // first half of sub-position 3 (taps 0, 1)
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* smem, int lds_off, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)(smem + lds_off), 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ int fastdiv(int n, unsigned magic) { return magic ? (int)__umulhi((unsigned)n, magic) : n; }
 
-template <int OFF>
-__device__ __forceinline__ void lds_read16(bf16x8& dst, int addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-__device__ __forceinline__ void mfma1(f32x16& acc, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
 
 // Operand registers of a wave: up to four halo fragments per 16-channel k-step, double-buffered by k-step; the four weight
 // fragments (this wave's four 32-channel output groups) of one (slot, k-step) step, double-buffered by step.
@@ -169,11 +153,10 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_s2d_fwd_kernel(ConvKParams p,
     const int stages_per_tile = nch2 + 5 * nchC;
 
     // static tile list, XCD-contiguous (conv_pipe.hip): the channel groups of one pixel tile are neighbours
-    const int xcd = blockIdx.x & 7, bslot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-    const int tq = sa.total_tiles >> 3, tr = sa.total_tiles & 7;
-    const int xs = xcd * tq + (xcd < tr ? xcd : tr), xn = tq + (xcd < tr ? 1 : 0);
+    int xs, xn, bslot, nslots;
+    xcd_tile_span(sa.total_tiles, xs, xn, bslot, nslots);
     if (bslot >= xn) return;
-    const int my_tiles = (xn - bslot + nslots - 1) / nslots;
+    const int my_tiles = xcd_my_tiles(xn, bslot, nslots);
     auto decode = [&](int k, int& b, int& y0, int& x0, int& n0) {
         const int t = xs + bslot + k * nslots;
         int pt = fastdiv(t, sa.m_ng);
@@ -480,26 +463,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_s2d_fwd_kernel(ConvKParams p,
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tail DMAs must not outlive the block's LDS allocation
 }
 
-int g_sf_cus = 0;
-unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
 
 template <int TW, int NT, int NW, int NF>
 int launch_sf(const ConvKParams& p, hipStream_t s) {
     using Cfg = FwCfg<TW, NT, NW, NF>;
-    static int attr_state = 0;
-    if (attr_state == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_s2d_fwd_kernel<TW, NT, NW, NF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-        attr_state = e == hipSuccess ? 1 : -1;
-    }
-    if (attr_state < 0) return STYLEX_NOT_APPLICABLE;
-    if (!g_sf_cus) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        g_sf_cus = n > 0 ? (n & ~7) : 256;
-        if (g_sf_cus < 8) g_sf_cus = 8;
-    }
+    if (stylex_dynamic_lds_once<conv_s2d_fwd_kernel<TW, NT, NW, NF>>(Cfg::SMEM) != hipSuccess) return STYLEX_NOT_APPLICABLE;
     const int tiles_x = p.Wo / TW, tiles_y = p.Ho / Cfg::TH, ngs = p.N / NT;
     SfArgs sa;
     sa.total_tiles = p.B * tiles_x * tiles_y * ngs;
@@ -507,7 +475,7 @@ int launch_sf(const ConvKParams& p, hipStream_t s) {
     sa.m_tpi = magic_of(tiles_x * tiles_y);
     sa.m_tx = magic_of(tiles_x);
     stylex_note_kernel("conv_s2d_fwd_kernel<%d, %d, %d, %d>", TW, NT, NW, NF);
-    const int blocks = NW == 4 ? 2 * g_sf_cus : g_sf_cus;  // 4-wave blocks: two per CU
+    const int blocks = NW == 4 ? 2 * stylex_cu_count() : stylex_cu_count();  // 4-wave blocks: two per CU
     hipLaunchKernelGGL((conv_s2d_fwd_kernel<TW, NT, NW, NF>), dim3((unsigned)blocks), dim3(NW * 64), Cfg::SMEM, s, p, sa);
     return (int)hipGetLastError();
 }

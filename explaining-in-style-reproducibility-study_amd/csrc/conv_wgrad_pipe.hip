@@ -30,10 +30,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // kernel argument (outside the anonymous namespace: a kernel's host stub needs externally visible parameter types)
@@ -47,7 +46,6 @@ struct StylexWgPipeArgs {
 namespace {
 
 typedef StylexWgPipeArgs WgArgs;
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 // NP64 = 64-channel dy panels per stage (block tile 64*NP64 output channels), TW = tile width in pixels.
 // A stage is PX output pixels (TR rows x TW) with its (TR+2) x (TW+2) halo of x; every wave multiplies 128 of them.
@@ -77,14 +75,7 @@ struct WgCfg {
     static constexpr int NSTEP = PWS * (RW + 2);          // steps (halo row, k-step column) per stage: 12 / 10 / 6
 };
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* smem, int lds_off, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)(smem + lds_off), 16, voff, soff, 0, 0);
-}
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // LDS transpose read (4 consecutive pixels of this lane's channel) as inline asm: hipcc puts vmcnt(0) in front of every
 // LDS read it can see behind a buffer-load-to-LDS and sinks the reads next to their MFMAs (conv_pipe.hip).
@@ -93,9 +84,6 @@ __device__ __forceinline__ void tr_read(s16x4& dst, int addr) {
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
 }
 
-__device__ __forceinline__ void mfma1(f32x16& acc, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
 
 __device__ __forceinline__ bf16x8 cat8(const s16x4& lo, const s16x4& hi) {
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -518,13 +506,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_pipe_kernel(ConvKParams 
 template <int NP64, int TW>
 int launch_wg_s2d(const ConvKParams& p, const WgArgs& wa, int blocks, hipStream_t s) {
     using Cfg = WgCfg<NP64, TW>;
-    static int attr_state = 0;
-    if (attr_state == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_pipe_kernel<NP64, TW, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-        attr_state = e == hipSuccess ? 1 : -1;
-    }
-    if (attr_state < 0) return STYLEX_NOT_APPLICABLE;
+    if (stylex_dynamic_lds_once<conv3x3_wgrad_pipe_kernel<NP64, TW, false, true>>(Cfg::SMEM) != hipSuccess) return STYLEX_NOT_APPLICABLE;
     stylex_note_kernel("conv3x3_wgrad_pipe_kernel<%d, %d, false, true>", NP64, TW);
     hipLaunchKernelGGL((conv3x3_wgrad_pipe_kernel<NP64, TW, false, true>), dim3(blocks), dim3(512), Cfg::SMEM, s, p, wa);
     return (int)hipGetLastError();
@@ -533,22 +515,18 @@ int launch_wg_s2d(const ConvKParams& p, const WgArgs& wa, int blocks, hipStream_
 template <int NP64, int TW>
 int launch_wg(const ConvKParams& p, const WgArgs& wa, int blocks, bool bias, hipStream_t s) {
     using Cfg = WgCfg<NP64, TW>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_pipe_kernel<NP64, TW, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-        if (e != hipSuccess) return STYLEX_NOT_APPLICABLE;  // a device with less LDS: the older kernels serve the launch
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_pipe_kernel<NP64, TW, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-        if (e != hipSuccess) return STYLEX_NOT_APPLICABLE;
-        attr_done = true;
-    }
+    // refused (a device with less LDS): the older kernels serve the launch
+    if (stylex_dynamic_lds_once<conv3x3_wgrad_pipe_kernel<NP64, TW, true>>(Cfg::SMEM) != hipSuccess ||
+        stylex_dynamic_lds_once<conv3x3_wgrad_pipe_kernel<NP64, TW, false>>(Cfg::SMEM) != hipSuccess)
+        return STYLEX_NOT_APPLICABLE;
     stylex_note_kernel("conv3x3_wgrad_pipe_kernel<%d, %d, %s, false>", NP64, TW, bias ? "true" : "false");
     if (bias) hipLaunchKernelGGL((conv3x3_wgrad_pipe_kernel<NP64, TW, true>), dim3(blocks), dim3(512), Cfg::SMEM, s, p, wa);
     else hipLaunchKernelGGL((conv3x3_wgrad_pipe_kernel<NP64, TW, false>), dim3(blocks), dim3(512), Cfg::SMEM, s, p, wa);
     return (int)hipGetLastError();
 }
 
+// CUs as the split plan counts them: the device's number itself, cached per process (not stylex_cu_count(), which rounds
+// down to whole XCDs for the grids of the persistent kernels)
 int g_wg_cus = 0;
 
 }  // namespace

@@ -21,21 +21,13 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "conv_prims.h"
 #include "stylex_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    f32x2_t v = {lo, hi};
-    bf16x2_t r = __builtin_convertvector(v, bf16x2_t);
-    return *reinterpret_cast<unsigned*>(&r);
-}
 
 typedef __attribute__((address_space(3))) s16x4* lds_s4_ptr;
 
@@ -97,8 +89,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_tr_kernel(ConvKParams p) {
     auto scaled = [&](uint4 v, const float* sc) -> uint4 {
         float4 a0 = *reinterpret_cast<const float4*>(sc), a1 = *reinterpret_cast<const float4*>(sc + 4);
         float4 f0 = act_unpack4(make_uint2(v.x, v.y)), f1 = act_unpack4(make_uint2(v.z, v.w));
-        v.x = pack_bf16(f0.x * a0.x, f0.y * a0.y); v.y = pack_bf16(f0.z * a0.z, f0.w * a0.w);
-        v.z = pack_bf16(f1.x * a1.x, f1.y * a1.y); v.w = pack_bf16(f1.z * a1.z, f1.w * a1.w);
+        v.x = act_pack2(f0.x * a0.x, f0.y * a0.y); v.y = act_pack2(f0.z * a0.z, f0.w * a0.w);
+        v.z = act_pack2(f1.x * a1.x, f1.y * a1.y); v.w = act_pack2(f1.z * a1.z, f1.w * a1.w);
         return v;
     };
 
@@ -298,7 +290,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_tr_dma_kernel(ConvKParams p
     const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a2), 0, 0x7ffffff0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, 0x7ffffff0, 0x00020000);
     constexpr unsigned OOBV = 0x80000000u;
-    typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
     // ---- staging: DMA instruction `it` of a stage = pixel rows it * 16 + (lane >> 2) of this wave's panel, slot lane & 3
     const bool stage_x = wave >= 4;
@@ -410,13 +401,8 @@ template <int TN_, int TC_, bool C8>
 int launch_tr(const ConvKParams& p, int blocks, hipStream_t s) {
     auto k = conv_wgrad_tr_kernel<TN_, TC_, C8>;
     constexpr int smem_bytes = TrGeom<TN_, TC_>::SMEM_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           smem_bytes);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    const hipError_t e = stylex_dynamic_lds_once<conv_wgrad_tr_kernel<TN_, TC_, C8>>(smem_bytes);
+    if (e != hipSuccess) return (int)e;
     stylex_note_kernel("conv_wgrad_tr_kernel<%d, %d, %s>", TN_, TC_, C8 ? "true" : "false");
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), smem_bytes, s, p);
     return (int)hipGetLastError();
@@ -470,13 +456,8 @@ int stylex_launch_wgrad_tr(ConvKParams p, float* partial, hipStream_t s, int* sp
     const int T = p.KH * p.KW;
     if (mode == 2) return launch_tr<1, 2, true>(p, ((p.N + 63) / 64) * splits, s);
     if (mode == 0 && tr_dma_applicable(p)) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_tr_dma_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, DSTAGES * DSTAGE_BYTES);
-            if (e != hipSuccess) return (int)e;
-            attr_done = true;
-        }
+        const hipError_t e = stylex_dynamic_lds_once<conv_wgrad_tr_dma_kernel>(DSTAGES * DSTAGE_BYTES);
+        if (e != hipSuccess) return (int)e;
         stylex_note_kernel("conv_wgrad_tr_dma_kernel");
         hipLaunchKernelGGL(conv_wgrad_tr_dma_kernel, dim3((p.N / 128) * (p.Ck / 128) * T * splits), dim3(512), DSTAGES * DSTAGE_BYTES, s, p);
         return (int)hipGetLastError();

@@ -131,6 +131,17 @@ void fill_common(ConvKParams& p, const int64_t* sh) {
 
 }  // namespace
 
+int stylex_cu_count() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        n = n > 0 ? (n & ~7) : 256;
+        return n < 8 ? 8 : n;
+    }();
+    return cus;
+}
+
 void stylex_note_kernel(const char* fmt, ...) {
     if (!g_timing) return;
     va_list ap;

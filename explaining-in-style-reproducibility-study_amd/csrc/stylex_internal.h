@@ -61,6 +61,21 @@ int stylex_launch_pack(const float* w, void* wf, void* wb, int N, int C, int T, 
 
 #define STYLEX_NOT_APPLICABLE (-100)
 
+// Compute units of the current device rounded down to a multiple of 8 (one block per CU, whole XCDs: the grid of the
+// persistent kernels); 256 if the query fails, at least 8.  Asked once per PROCESS: a process that switches between
+// devices of different sizes keeps the first answer (as the per-file copies this replaces did).
+int stylex_cu_count();
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of one kernel instantiation, set at the first call; every call returns
+// what that attempt returned (the outcome depends on the kernel, the size and the device only).  What a refusal means
+// is the launcher's business: an error, or STYLEX_NOT_APPLICABLE where an older kernel serves the launch.
+template <auto Kernel>
+hipError_t stylex_dynamic_lds_once(int bytes) {
+    static const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return e;
+}
+
 // Timing hook (stylex_timing_kernels): a launcher names the kernel it is about to launch, as rocprofv3 prints it
 // (printf-style; thread-local, no allocation).  A timed C-ABI call attributes its hipEvent interval to the LAST name
 // noted inside it (the main kernel of a multi-launch call notes itself last).
