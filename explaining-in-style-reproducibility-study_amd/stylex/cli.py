@@ -43,6 +43,7 @@ DEFAULTS = dict(
     tensorboard_dir="tb_logs_stylex",
     # MI355X additions
     precision="fp32",
+    fid_weights=None,  # Inception weights of --calculate_fid_every: a path or random:<seed> (fid_inception.resolve_weights)
 )
 
 # train_from_folder kwarg -> Trainer kwarg, where the names differ

@@ -126,6 +126,11 @@ SIGNATURES = {
     "stylex_nhwc_bf16_to_nchw_f32": (ctypes.c_int, [_c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_resize_norm_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _i64p, _i64p, ctypes.c_void_p]),
     "stylex_resize_norm_bwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_void_p]),
+    "stylex_fid_prep": (ctypes.c_int, [_c_f, _c_f, _i64p, _i64p, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_affine_act_nchw_slice_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_int64,
+                                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "stylex_fid_moments_acc": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_void_p]),
     "stylex_relu_gate_add": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_maxpool3s2_nhwc_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_void_p]),
     "stylex_maxpool3s2_nhwc_bwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_void_p]),
@@ -990,6 +995,45 @@ def resize_norm_bwd(gy, in_hw, std=None):
     _check(lib.stylex_resize_norm_bwd(_ptr(gy), _ptr(gx), _ptr(std), _shape(b, c, int(in_hw[0]), int(in_hw[1]), ho, wo), _stream()),
            "stylex_resize_norm_bwd")
     return gx
+
+
+def fid_prep(x, size=299):
+    """Image batch [B, >= 3, H, W] (fp32 or bf16, any strides) -> Inception input [B, 3, size, size], dense fp32: 8-bit
+    quantisation, / 255, bilinear resize, 2 v - 1 in one launch (stylex_fid_prep)."""
+    lib = _ensure_device(x)
+    assert x.dim() == 4 and x.shape[1] >= 3 and x.dtype in (torch.float32, torch.bfloat16)
+    b, _, h, w = x.shape
+    y = torch.empty((b, 3, int(size), int(size)), dtype=torch.float32, device=x.device)
+    _check(lib.stylex_fid_prep(_ptr(x), _ptr(y), _shape(b, h, w, int(size), int(size)), _shape(*x.stride()),
+                               int(x.dtype == torch.bfloat16), _stream()), "stylex_fid_prep")
+    return y
+
+
+def affine_act_slice_fwd(x, scale, shift, out, c0, relu=True):
+    """act(x * scale[c] + shift[c]) of a dense fp32 NCHW x written into channels c0 .. c0 + C - 1 of the dense fp32 NCHW tensor
+    `out` (same batch and spatial size): the tail of a branch lands in its slice of the concatenated output
+    (stylex_affine_act_nchw_slice_fwd)."""
+    lib = _ensure_device(x)
+    b, c, h, w = _dense_f32(x).shape
+    bo, ct, ho, wo = _dense_f32(out).shape
+    assert (bo, ho, wo) == (b, h, w) and 0 <= c0 and c0 + c <= ct, (tuple(x.shape), tuple(out.shape), c0)
+    dst = ctypes.c_void_p(out.data_ptr() + 4 * c0 * h * w)
+    _check(lib.stylex_affine_act_nchw_slice_fwd(_ptr(x), _ptr(scale), _ptr(shift), None, dst, b, c, h * w, ct * h * w, int(relu),
+                                                _stream()), "stylex_affine_act_nchw_slice_fwd")
+    return out
+
+
+def fid_moments_acc(x, total, gram):
+    """Pooled features of the map x [B, D, h, w] (dense fp32) and their running moments: total[d] += sum_b f, gram[i][j] +=
+    sum_b f_i f_j for i <= j, both fp64 and updated in place; returns f [B, D] fp32 (stylex_fid_moments_acc)."""
+    lib = _ensure_device(x)
+    b, d, h, w = _dense_f32(x).shape
+    assert total.dtype == torch.float64 and gram.dtype == torch.float64 and total.is_contiguous() and gram.is_contiguous()
+    assert tuple(total.shape) == (d,) and tuple(gram.shape) == (d, d) and total.device == x.device == gram.device
+    feat = torch.empty((b, d), dtype=torch.float32, device=x.device)
+    _check(lib.stylex_fid_moments_acc(_ptr(x), _ptr(feat), _ptr(total), _ptr(gram), b, d, h * w, _stream()),
+           "stylex_fid_moments_acc")
+    return feat
 
 
 def relu_gate_add(a, b, y):

@@ -652,7 +652,7 @@ class Trainer:
                  # --- extensions (defaults reproduce the reference) ---
                  classifier=None, lpips_fn=None, gp_every=4, pl_every=32, pl_after=5000, device=None,
                  save_training_state=False, graphs=None, graph_warmup=4, new_architecture=False, device_pipeline=None,
-                 device_rng=None, *args, **kwargs):
+                 device_rng=None, fid_weights=None, *args, **kwargs):
         kl_rec_during_disc = kwargs.pop("kl_rec_during_disc", False)  # cli.py forwards it; only the new architecture reads it
         # new_architecture = the conditional-D variant the reference ships as stylex_train_new.py (cli.py:17-22)
         self.new_architecture = bool(new_architecture)
@@ -717,6 +717,9 @@ class Trainer:
         self.dataset_aug_prob = dataset_aug_prob
         self.calculate_fid_every, self.calculate_fid_num_images = calculate_fid_every, calculate_fid_num_images
         self.clear_fid_cache = clear_fid_cache
+        # Inception weights of calculate_fid: a path, "random:<seed>" (tests, timing) or None = $STYLEX_FID_WEIGHTS, then
+        # torch hub's checkpoint folder (fid_inception.resolve_weights); read at the first FID step
+        self.fid_weights, self._fid_eval = fid_weights, None
         self.is_ddp, self.is_main, self.rank, self.world_size = is_ddp, rank == 0, rank, world_size
         self.sample_from_encoder = sample_from_encoder
         self.logger = None
@@ -1364,6 +1367,8 @@ class Trainer:
                 self.evaluate(encoder_input=self.sample_from_encoder, num=floor(self.steps / self.evaluate_every))
             if exists(self.calculate_fid_every) and self.steps % self.calculate_fid_every == 0 and self.steps != 0:
                 self.last_fid = self.calculate_fid(math.ceil(self.calculate_fid_num_images / self.batch_size))
+                with open(str(self.results_dir / self.name / "fid_scores.txt"), "a") as f:  # reference :1500-1503
+                    f.write(f"{self.steps},{self.last_fid}\n")
         self.steps += 1
         self.av = None
 
@@ -1593,8 +1598,43 @@ class Trainer:
         grid(imgs, str(out_dir / f"{num}-{tag}-mr.png"))
 
     @torch.no_grad()
+    @_own_rng_mode
     def calculate_fid(self, num_batches):
-        raise RuntimeError("FID needs pytorch_fid + Inception weights (network) — out of scope offline")
+        """FID between `num_batches` loader batches and as many batches of truncated EMA samples (reference :1577-1622,
+        stylex_train_new.py:1667-1711), without files: the batches go through stylex_fid_prep (the 8-bit quantisation an
+        image file applies, resize to 299 px), the FID Inception-v3 and the fp64 moments kernel on the GPU (fid.py).  The
+        real statistics are kept in fid_dir/real_stats.npz, as the reference keeps its folder of real images: reused unless
+        clear_fid_cache is set or they were made at another image size / with other Inception weights.  Rank 0 only.
+        Not the reference's: generated images are quantised to 8 bits but not JPEG-compressed (image_extension)."""
+        if not self.is_main:
+            return None
+        import fid
+        import fid_inception
+
+        m = self.StylEx
+        if self._fid_eval is None:
+            self._fid_eval = fid.FIDEvaluator(fid_inception.build(self.fid_weights, self.device))
+        ev = self._fid_eval
+        tag = "image_size=%d;weights=%s" % (self.image_size, ev.net.weights_id)
+        cache = self.fid_dir / "real_stats.npz"
+        ev.real = None if self.clear_fid_cache else fid.FIDStats.load(cache, tag, self.device)
+        if ev.real is None:
+            for _ in range(num_batches):
+                ev.add_real(self._next_batch())
+            ev.real.save(cache, tag)
+        ev.fake = None
+        m.eval()
+        for _ in range(num_batches):
+            latents = noise_list(self.batch_size, m.G.num_layers, self._z_dim, device=self.device)
+            n = image_noise(self.batch_size, m.G.image_size, device=self.device)
+            probs = None
+            if self.new_architecture:
+                # stylex_train_new.py:1700-1705 calls generate_truncated without class probabilities, which its own
+                # generate_truncated (:1741-1745) cannot concatenate: drawn as evaluate draws them (:1618-1620)
+                probs = torch.rand(self.batch_size, 2, device=self.device)
+                probs = probs / torch.sum(probs, dim=1, keepdim=True)
+            ev.add_fake(self.generate_truncated(m.SE, m.GE, latents, n, trunc_psi=self.trunc_psi, probabilities=probs))
+        return ev.value()
 
     @torch.no_grad()
     @_own_rng_mode

@@ -296,6 +296,31 @@ int stylex_resize_norm_fwd(const float* x, float* y, const float* mean, const fl
                            void* stream);
 int stylex_resize_norm_bwd(const float* gy, float* gx, const float* stdv, const int64_t* sh, void* stream);
 
+/* ---- Frechet Inception Distance on the device (stylex/fid.py, stylex/fid_inception.py), csrc/fid.hip -------------------
+ * The reference (stylex_train.py:1577-1622) writes real and generated images to files and hands the folders to the
+ * pytorch_fid package; here the batches stay on the GPU between the generator / loader and the statistics.
+ *
+ * stylex_fid_prep: image batch -> Inception input, one pass.  sh = {B, Hi, Wi, Ho, Wo}; x [B][>= 3][Hi][Wi], fp32 or bf16
+ *   (x_is_bf16), read through its element strides {b, c, h, w} (non-negative; any layout, a channel slice included); only
+ *   channels 0..2 are read.  Per element q = floor(clamp(x * 255 + 0.5, 0, 255)) (the byte of an image file), then q / 255,
+ *   the bilinear resize with the index rule of stylex_resize_norm_fwd, then 2 v - 1.  y dense fp32 [B][3][Ho][Wo].
+ *
+ * stylex_affine_act_nchw_slice_fwd: stylex_affine_act_nchw_fwd whose output rows are `y_batch_stride` elements apart
+ *   (>= C * HW): y[b * y_batch_stride + c * HW + p].  With y pointing at channel c0 of a dense [B][Ct][HW] tensor and
+ *   y_batch_stride = Ct * HW it writes channels c0 .. c0 + C - 1 of that tensor — bit for bit what the dense entry point
+ *   followed by a concatenation gives.  x, residual dense [B][C][HW].
+ *
+ * stylex_fid_moments_acc: x [B][D][HW] fp32 (the last feature map), D % 16 == 0.  f[b][d] = (sum_p x[b][d][p]) / HW in
+ *   fp32, added in index order with a compensation term (Kahan), stored to feat [B][D]; feat may be NULL only when HW == 1 (x is f then).  Then
+ *   sum[d] += sum_b f[b][d] and gram[i][j] += sum_b f[b][i] * f[b][j] for i <= j (gram [D][D], fp64, row-major; the
+ *   elements below the diagonal are neither read nor written).  fp64 products on v_mfma_f64_16x16x4_f64; one wave owns a
+ *   16 x 16 tile (reads, accumulates, writes it), b ascending in groups of 4 padded with zeros; no atomics: the same inputs
+ *   give the same bits.  x 16-byte aligned when HW % 4 == 0. */
+int stylex_fid_prep(const void* x, float* y, const int64_t* sh, const int64_t* strides, int x_is_bf16, void* stream);
+int stylex_affine_act_nchw_slice_fwd(const float* x, const float* scale, const float* shift, const float* residual, float* y,
+                                     int64_t B, int64_t C, int64_t HW, int64_t y_batch_stride, int relu, void* stream);
+int stylex_fid_moments_acc(const float* x, float* feat, double* sum, double* gram, int64_t B, int64_t D, int64_t HW, void* stream);
+
 /* ---- layout bridges: the library's dense fp32 NCHW tensors <-> this library's bf16 NHWC tensors (round 6) -------------
  * Where a frozen network keeps part of its path on the library's fp32 convolutions (the classifier forward, north_star; the
  * LPIPS stem) and the rest runs on the bf16 kernels: frozen_resnet._ResNetBodyHybrid, lpips_alex._taps_bf16.  C % 8 == 0.
