@@ -1302,10 +1302,20 @@ def conv2d_bwd_weight(x, dy, w_shape, stride, pad, precision, x_scale=None, dy_s
     return dw
 
 
-def _ew(fn_name, x, out_shape, in_shape_for_kernel):
+def _out_cl(out, shape, like):
+    """The output of an elementwise wrapper: a fresh channels_last tensor, or the caller's `out` (checked; it may be a view at
+    any element offset — the launchers pick the lane from the pointers' alignment)."""
+    if out is None:
+        return empty_cl(shape, like)
+    assert is_cl(out) and out.dtype == like.dtype and out.device == like.device and tuple(out.shape) == tuple(shape), \
+        (out.shape, out.dtype, shape, like.dtype)
+    return out
+
+
+def _ew(fn_name, x, out_shape, in_shape_for_kernel, out=None):
     lib = _ensure_device(x)
     assert is_cl(x) and x.dtype in (torch.float32, torch.bfloat16)
-    y = empty_cl(out_shape, x)
+    y = _out_cl(out, out_shape, x)
     b, c, h, w = in_shape_for_kernel
     _check(getattr(lib, fn_name)(_ptr(x), _ptr(y), _shape(b, h, w, c), _adt(x), _stream()), fn_name)
     return y
@@ -1321,29 +1331,29 @@ def upsample2x_bwd(dy):
     return _ew("stylex_upsample2x_bilinear_bwd", dy, (b, c, h2 // 2, w2 // 2), (b, c, h2 // 2, w2 // 2))
 
 
-def rgb_up_blur_add_fwd(rgb, prev=None):
+def rgb_up_blur_add_fwd(rgb, prev=None, out=None):
     """blur3x3_reflect(upsample2x(rgb + prev)) in one pass (RGBBlock.forward :622-626); prev may be None."""
     lib = _ensure_device(rgb)
     assert is_cl(rgb) and rgb.dtype in (torch.float32, torch.bfloat16)
     assert prev is None or (is_cl(prev) and prev.dtype == rgb.dtype and prev.shape == rgb.shape)
     b, c, h, w = rgb.shape
-    y = empty_cl((b, c, 2 * h, 2 * w), rgb)
+    y = _out_cl(out, (b, c, 2 * h, 2 * w), rgb)
     _check(lib.stylex_rgb_up_blur_add_fwd(_ptr(rgb), _ptr(prev), _ptr(y), _shape(b, h, w, c), _adt(rgb), _stream()),
            "stylex_rgb_up_blur_add_fwd")
     return y
 
 
-def rgb_up_blur_add_bwd(dy):
+def rgb_up_blur_add_bwd(dy, out=None):
     b, c, h2, w2 = dy.shape
-    return _ew("stylex_rgb_up_blur_add_bwd", dy, (b, c, h2 // 2, w2 // 2), (b, c, h2 // 2, w2 // 2))
+    return _ew("stylex_rgb_up_blur_add_bwd", dy, (b, c, h2 // 2, w2 // 2), (b, c, h2 // 2, w2 // 2), out)
 
 
-def blur3x3_fwd(x):
-    return _ew("stylex_blur3x3_reflect_fwd", x, tuple(x.shape), tuple(x.shape))
+def blur3x3_fwd(x, out=None):
+    return _ew("stylex_blur3x3_reflect_fwd", x, tuple(x.shape), tuple(x.shape), out)
 
 
-def blur3x3_bwd(dy):
-    return _ew("stylex_blur3x3_reflect_bwd", dy, tuple(dy.shape), tuple(dy.shape))
+def blur3x3_bwd(dy, out=None):
+    return _ew("stylex_blur3x3_reflect_bwd", dy, tuple(dy.shape), tuple(dy.shape), out)
 
 
 def blur3x3_s2d_fwd(x):
@@ -1417,11 +1427,11 @@ def subsample2_bwd(dy, full_hw):
     return _ew("stylex_subsample2_bwd", dy, (b, c, h, w), (b, c, h, w))
 
 
-def bias_act_fwd(x, bias=None, noise=None, noise_w=None, noise_b=None):
+def bias_act_fwd(x, bias=None, noise=None, noise_w=None, noise_b=None, out=None):
     lib = _ensure_device(x)
     assert is_cl(x)
     b, c, h, w = x.shape
-    y = empty_cl(tuple(x.shape), x)
+    y = _out_cl(out, tuple(x.shape), x)
     ns = 0
     bias, noise, noise_w, noise_b = _f32(bias), _f32(noise), _f32(noise_w), _f32(noise_b)
     if noise is not None:
@@ -1431,11 +1441,11 @@ def bias_act_fwd(x, bias=None, noise=None, noise_w=None, noise_b=None):
     return y
 
 
-def bias_act_bwd(dy, y):
+def bias_act_bwd(dy, y, out=None):
     lib = _ensure_device(dy)
     assert is_cl(dy) and is_cl(y) and dy.dtype == y.dtype
     b, c, h, w = dy.shape
-    dx = empty_cl(tuple(dy.shape), dy)
+    dx = _out_cl(out, tuple(dy.shape), dy)
     _check(lib.stylex_bias_act_bwd(_ptr(dy), _ptr(y), _ptr(dx), _shape(b, h, w, c), _adt(dy), _stream()),
            "stylex_bias_act_bwd")
     return dx

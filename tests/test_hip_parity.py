@@ -3072,6 +3072,46 @@ def test_fused_loss_kernels_match_the_torch_compositions():
     close((xa.double() - hb16.double()).abs().mean(), out, tol, "l1 bf16 value")
     assert xb.grad.dtype == torch.bfloat16
     close(-torch.sign(xa.double() - hb16.double()) / xa.numel(), xb.grad, 1e-2, "l1 bf16 grad")
+    # the sizes at which l1_partial_kernel's 1024 blocks of 8 x 256 elements wrap their grid-stride loop (> 2,097,152 elements)
+    # and l1_finish_kernel takes four passes over the partials.  Integer operands in [-3, 3] with planted equal pairs: the sum
+    # stays below 2^24, so every fp32 partial sum is exact in any order, the value is the IEEE quotient fp32(S) / fp32(n) and
+    # every gradient element is +-fp32(1 / n) or 0, exactly.
+    def ints(*shape):
+        return torch.randint(-3, 4, shape, generator=g).float()
+
+    def quotient(s, n):
+        assert s < 2 ** 24 and n < 2 ** 24
+        return torch.tensor(float(s)) / torch.tensor(float(n))  # one fp32 division, as the kernel's s / (float)n
+
+    a, b_ = ints(2, 3, 600, 600), ints(2, 3, 600, 600)
+    b_[:, :, ::7, :5] = a[:, :, ::7, :5]
+    b_.view(-1)[-3:] = a.view(-1)[-3:]
+    n = a.numel()
+    assert n > 1024 * 8 * 256
+    ad, bd = a.to(DEV).requires_grad_(), b_.to(DEV).requires_grad_()
+    out = ops.l1_mean(ad, bd)
+    assert type(out.grad_fn).__name__ == "_L1MeanBackward"
+    out.backward()
+    sgn = torch.sign(a - b_)
+    assert torch.equal(out.cpu(), quotient(int((a - b_).abs().sum().item()), n)), "l1 dense at the wrap size: value"
+    assert torch.equal(ad.grad.cpu(), sgn * quotient(1, n)) and torch.equal(bd.grad.cpu(), -sgn * quotient(1, n)), \
+        "l1 dense at the wrap size: gradients"
+    real, gen4 = ints(3, 3, 500, 500), ints(3, 4, 500, 500)
+    gen4[:, :3, ::9, :4] = real[:, :, ::9, :4]
+    gen4[-1, :3, -1, -2:] = real[-1, :, -1, -2:]
+    n = real.numel()
+    assert n > 1024 * 8 * 256
+    x4 = gen4.to(DEV).contiguous(memory_format=torch.channels_last).requires_grad_()
+    gen = x4[:, :3]
+    assert not gen.is_contiguous() and not gen.permute(0, 2, 3, 1).is_contiguous()
+    out = ops.l1_mean(real.to(DEV), gen)
+    assert type(out.grad_fn).__name__ == "_L1MeanBackward"
+    out.backward()
+    sgn = torch.sign(real - gen4[:, :3])
+    assert torch.equal(out.cpu(), quotient(int((real - gen4[:, :3]).abs().sum().item()), n)), "l1 strided at the wrap size: value"
+    assert x4.grad.shape == x4.shape and x4.grad.stride() == x4.stride()
+    assert torch.equal(x4.grad[:, :3].cpu(), -sgn * quotient(1, n)), "l1 strided at the wrap size: gradient at the strided offsets"
+    assert (x4.grad[:, 3] == 0).all(), "l1 strided at the wrap size: the fourth channel's gradient"
     # not expressible as a walk (broadcast operand): the torch composition answers
     out = ops.l1_mean(torch.zeros(1, 8, 1, 1, device=DEV).expand(4, 8, 6, 6), xb.detach().float())
     close(hb16.double().abs().mean(), out, 1e-6, "l1 broadcast fallback")
