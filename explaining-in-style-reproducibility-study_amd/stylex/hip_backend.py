@@ -131,6 +131,19 @@ SIGNATURES = {
                                                         ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "stylex_fid_moments_acc": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_void_p]),
+    "stylex_bn_train_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "stylex_bn_stats_nchw": (ctypes.c_int, [_c_f] * 5 + [ctypes.c_double, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "stylex_bn_act_nchw_fwd": (ctypes.c_int, [_c_f] * 7 + [ctypes.c_double, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int, ctypes.c_void_p]),
+    "stylex_bn_act_nchw_bwd_reduce": (ctypes.c_int, [_c_f] * 7 + [ctypes.c_double, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "stylex_bn_act_nchw_bwd_apply": (ctypes.c_int, [_c_f] * 10 + [ctypes.c_double, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                    ctypes.c_int, ctypes.c_void_p]),
+    "stylex_softmax_ce_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "stylex_softmax_ce_fwd": (ctypes.c_int, [_c_f] * 4 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_void_p]),
+    "stylex_softmax_ce_bwd": (ctypes.c_int, [_c_f] * 4 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_relu_gate_add": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_maxpool3s2_nhwc_fwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_void_p]),
     "stylex_maxpool3s2_nhwc_bwd": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, ctypes.c_void_p]),
@@ -953,6 +966,119 @@ def affine_act_bwd(gy, y, scale, relu=True, want_res=False):
                                           _ptr(gres) if want_res else None, b, c, h * w, int(relu), _stream()),
            "stylex_affine_act_nchw_bwd")
     return gx, gres
+
+
+BN_ACTS = {"none": 0, "relu": 1, "relu6": 2}  # the `act` argument of the stylex_bn_act_nchw_* entry points
+
+
+def _workspace(nbytes, like):
+    """`nbytes` of workspace as an fp32 tensor (through _empty: poisoned and guarded in the STYLEX_POISON modes)."""
+    return _empty(((int(nbytes) + 3) // 4,), dtype=torch.float32, device=like.device)
+
+
+def _bn_workspace(lib, b, c, hw, like, workspace=None):
+    """(workspace, bytes) of the two batch-norm reductions; `workspace`: the caller's own fp32 tensor of at least that size."""
+    nbytes = lib.stylex_bn_train_workspace_bytes(b, c, hw)
+    if nbytes < 0:
+        raise StylexHipError("stylex_bn_train_workspace_bytes rejects B=%d C=%d HW=%d" % (b, c, hw))
+    if workspace is None:
+        return _workspace(nbytes, like), nbytes
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() * 4 >= nbytes
+    return workspace, nbytes
+
+
+def bn_stats(x, running_mean=None, running_var=None, momentum=0.1, workspace=None):
+    """Per-channel mean and biased variance of a dense fp32 NCHW tensor over (B, H, W); with running_mean / running_var (fp32,
+    updated in place) also nn.BatchNorm2d's running-statistics update (stylex_bn_stats_nchw)."""
+    lib = _ensure_device(x)
+    b, c, h, w = _dense_f32(x).shape
+    ws, nbytes = _bn_workspace(lib, b, c, h * w, x, workspace)
+    mean = _empty((c,), dtype=torch.float32, device=x.device)
+    var = _empty((c,), dtype=torch.float32, device=x.device)
+    if running_mean is not None:
+        assert _dense_f32(running_mean).shape == (c,) and _dense_f32(running_var).shape == (c,)
+    _check(lib.stylex_bn_stats_nchw(_ptr(x), _ptr(mean), _ptr(var), _ptr(running_mean), _ptr(running_var), float(momentum), b, c,
+                                    h * w, _ptr(ws), nbytes, _stream()), "stylex_bn_stats_nchw")
+    return mean, var
+
+
+def bn_act_fwd(x, mean, var, gamma, beta, eps, residual=None, act="none"):
+    """act((x - mean[c]) * rsqrt(var[c] + eps) * gamma[c] + beta[c] (+ residual)), one pass (stylex_bn_act_nchw_fwd)."""
+    lib = _ensure_device(x)
+    b, c, h, w = _dense_f32(x).shape
+    if residual is not None:
+        assert _dense_f32(residual).shape == x.shape
+    y = _empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    _check(lib.stylex_bn_act_nchw_fwd(_ptr(x), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), _ptr(residual), _ptr(y), float(eps),
+                                      b, c, h * w, BN_ACTS[act], _stream()), "stylex_bn_act_nchw_fwd")
+    return y
+
+
+def bn_act_bwd_reduce(gy, y, x, mean, var, eps, act="none", workspace=None):
+    """(dgamma, dbeta) = (sum g * xhat, sum g) per channel, g = gy * gate(y) (stylex_bn_act_nchw_bwd_reduce); y may be None
+    without an activation."""
+    lib = _ensure_device(gy)
+    b, c, h, w = _dense_f32(gy).shape
+    assert _dense_f32(x).shape == gy.shape and (y is None or _dense_f32(y).shape == gy.shape)
+    ws, nbytes = _bn_workspace(lib, b, c, h * w, gy, workspace)
+    dgamma = _empty((c,), dtype=torch.float32, device=gy.device)
+    dbeta = _empty((c,), dtype=torch.float32, device=gy.device)
+    _check(lib.stylex_bn_act_nchw_bwd_reduce(_ptr(gy), _ptr(y), _ptr(x), _ptr(mean), _ptr(var), _ptr(dgamma), _ptr(dbeta),
+                                             float(eps), b, c, h * w, BN_ACTS[act], _ptr(ws), nbytes, _stream()),
+           "stylex_bn_act_nchw_bwd_reduce")
+    return dgamma, dbeta
+
+
+def bn_act_bwd_apply(gy, y, x, mean, var, gamma, dgamma, dbeta, eps, act="none", want_gx=True, want_res=False):
+    """(gx, gres): gx = gamma * invstd * (g - dbeta / n - xhat * dgamma / n), gres = g (stylex_bn_act_nchw_bwd_apply)."""
+    lib = _ensure_device(gy)
+    b, c, h, w = _dense_f32(gy).shape
+    assert want_gx or want_res
+    gx = _empty(tuple(gy.shape), dtype=torch.float32, device=gy.device) if want_gx else None
+    gres = _empty(tuple(gy.shape), dtype=torch.float32, device=gy.device) if want_res else None
+    _check(lib.stylex_bn_act_nchw_bwd_apply(_ptr(gy), _ptr(y), _ptr(x) if want_gx else None, _ptr(mean), _ptr(var), _ptr(gamma),
+                                            _ptr(dgamma), _ptr(dbeta), _ptr(gx), _ptr(gres), float(eps), b, c, h * w,
+                                            BN_ACTS[act], _stream()), "stylex_bn_act_nchw_bwd_apply")
+    return gx, gres
+
+
+SOFTMAX_CE_MAX_K = 1024
+
+
+def _ce_args(logits, targets):
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous(), "logits: dense fp32 [B, K]"
+    assert targets.dtype == torch.int64 and targets.is_contiguous() and tuple(targets.shape) == (logits.shape[0],)
+    return int(logits.shape[0]), int(logits.shape[1])
+
+
+def softmax_ce_fwd(logits, targets, workspace=None, n_correct=None):
+    """(loss, n_correct): the mean cross-entropy of fp32 logits [B, K <= 1024] against int64 targets as an fp32 device scalar,
+    and the number of rows whose argmax equals the target as an int64 device scalar (stylex_softmax_ce_fwd).  workspace (fp32,
+    2 B elements) and n_correct (int64, one element) may be the caller's own tensors."""
+    lib = _ensure_device(logits)
+    b, k = _ce_args(logits, targets)
+    nbytes = lib.stylex_softmax_ce_workspace_bytes(b, k)
+    if nbytes < 0:
+        raise StylexHipError("stylex_softmax_ce_workspace_bytes rejects B=%d K=%d" % (b, k))
+    ws = _workspace(nbytes, logits) if workspace is None else workspace
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() * 4 >= nbytes
+    loss = _empty((), dtype=torch.float32, device=logits.device)
+    if n_correct is None:
+        n_correct = torch.empty((), dtype=torch.int64, device=logits.device)
+    assert n_correct.dtype == torch.int64 and n_correct.numel() == 1 and n_correct.device == logits.device
+    _check(lib.stylex_softmax_ce_fwd(_ptr(logits), _ptr(targets), _ptr(loss), _ptr(n_correct), b, k, _ptr(ws), nbytes, _stream()),
+           "stylex_softmax_ce_fwd")
+    return loss, n_correct
+
+
+def softmax_ce_bwd(logits, targets, gloss):
+    """(softmax - onehot) * gloss / B (stylex_softmax_ce_bwd); gloss: an fp32 device scalar."""
+    lib = _ensure_device(logits)
+    b, k = _ce_args(logits, targets)
+    assert gloss.dtype == torch.float32 and gloss.numel() == 1 and gloss.is_cuda
+    g = _empty(tuple(logits.shape), dtype=torch.float32, device=logits.device)
+    _check(lib.stylex_softmax_ce_bwd(_ptr(logits), _ptr(targets), _ptr(gloss), _ptr(g), b, k, _stream()), "stylex_softmax_ce_bwd")
+    return g
 
 
 def affine_relu_maxpool_fwd(x, scale, shift, want_idx):

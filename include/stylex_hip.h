@@ -342,6 +342,42 @@ int stylex_nhwc_bf16_to_nchw_f32(const void* g, const void* gate, float* gx, int
 int stylex_maxpool3s2_nhwc_fwd(const void* x, void* y, void* idx, const int64_t* sh, void* stream);
 int stylex_maxpool3s2_nhwc_bwd(const void* gy, const void* idx, void* gx, const int64_t* sh, void* stream);
 
+/* ---- training-mode BatchNorm2d + activation, softmax cross-entropy (csrc/bn_train.hip; stylex/bn_train.py) -----------------
+ * For training the classifier that StylEx explains (reference stylex/train_mobilenet_classifier.py,
+ * classifier_training_celeba.ipynb).  Dense fp32 [B][C][HW] tensors; per-channel vectors [C]; n = B * HW >= 2.
+ * act: 0 none, 1 ReLU, 2 ReLU6.  Every reduction: per-block fp64 partials of consecutive chunks of a channel in the caller's
+ * workspace (the workspace query below, 8-byte aligned), combined in fixed order; no atomics, the same inputs give the same bits.
+ * 16-byte accesses when HW % 4 == 0 and the tensor pointers are 16-byte aligned, single elements otherwise.
+ *
+ * stylex_bn_stats_nchw: mean[c], var[c] (biased; the sum of (x - mean)^2 of a centred second pass, never E[x^2] - mean^2)
+ *   and, when running_mean / running_var are given (both or neither), rm = (1 - m) rm + m mean,
+ *   rv = (1 - m) rv + m var n / (n - 1).  n < 2: STYLEX_EINVAL.
+ * stylex_bn_act_nchw_fwd: y = act((x - mean) * rsqrt(var + eps) * gamma + beta (+ residual)); residual may be NULL.
+ * stylex_bn_act_nchw_bwd_reduce: g = gy * gate(y) (ReLU: y > 0; ReLU6: 0 < y < 6; none: all of gy, y may be NULL),
+ *   xhat = (x - mean) * rsqrt(var + eps);  dbeta[c] = sum g,  dgamma[c] = sum g * xhat.
+ * stylex_bn_act_nchw_bwd_apply: gx = gamma * invstd * (g - dbeta / n - xhat * dgamma / n), gres = g; gx or gres may be
+ *   NULL (not both; x may be NULL without gx).
+ * stylex_softmax_ce_fwd: logits [B][K] fp32, K <= 1024, targets [B] int64.  loss[0] = mean_b (logsumexp_b - logit[b][target_b])
+ *   (the row maximum is subtracted before the exponentials), n_correct[0] = rows whose argmax (lowest index on ties) equals the
+ *   target.  A target outside [0, K) is never used as an index: its row contributes NaN to the loss, is not counted as correct
+ *   and gets a zero gradient row.  stylex_softmax_ce_bwd: glogits = (softmax - onehot) * gloss[0] / B. */
+int64_t stylex_bn_train_workspace_bytes(int64_t B, int64_t C, int64_t HW);
+int stylex_bn_stats_nchw(const float* x, float* mean, float* var, float* running_mean, float* running_var, double momentum,
+                         int64_t B, int64_t C, int64_t HW, void* workspace, int64_t workspace_bytes, void* stream);
+int stylex_bn_act_nchw_fwd(const float* x, const float* mean, const float* var, const float* gamma, const float* beta,
+                           const float* residual, float* y, double eps, int64_t B, int64_t C, int64_t HW, int act, void* stream);
+int stylex_bn_act_nchw_bwd_reduce(const float* gy, const float* y, const float* x, const float* mean, const float* var,
+                                  float* dgamma, float* dbeta, double eps, int64_t B, int64_t C, int64_t HW, int act,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+int stylex_bn_act_nchw_bwd_apply(const float* gy, const float* y, const float* x, const float* mean, const float* var,
+                                 const float* gamma, const float* dgamma, const float* dbeta, float* gx, float* gres, double eps,
+                                 int64_t B, int64_t C, int64_t HW, int act, void* stream);
+int64_t stylex_softmax_ce_workspace_bytes(int64_t B, int64_t K);
+int stylex_softmax_ce_fwd(const float* logits, const int64_t* targets, float* loss, int64_t* n_correct, int64_t B, int64_t K,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+int stylex_softmax_ce_bwd(const float* logits, const int64_t* targets, const float* gloss, float* glogits, int64_t B, int64_t K,
+                          void* stream);
+
 /* ---- input gradient of a frozen network's first convolution (round 6) ---------------------------
  * The K x K / stride-S stem over the 3-channel image of the frozen classifier (torchvision ResNet conv1: 7 x 7 / 2 / pad 3,
  * reference stylex/resnet_classifier.py:19, 56-71) and of LPIPS-AlexNet (11 x 11 / 4 / pad 2, reference stylex_train.py:404):
