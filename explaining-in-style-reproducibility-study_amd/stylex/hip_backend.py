@@ -947,21 +947,31 @@ def _dense_f32(t):
     return t
 
 
-def affine_act_fwd(x, scale, shift, residual=None, relu=True):
+def _out_as(out, shape, dtype, like, cl=False, make=None):
+    """The output of a frozen-network wrapper: a fresh tensor, or the caller's `out` (checked: dtype, shape, device, dense in the
+    layout the kernel writes; it may be a view at any element offset — the launchers test the pointers they need aligned)."""
+    if out is None:
+        return make() if make is not None else torch.empty(shape, dtype=dtype, device=like.device)
+    assert out.dtype == dtype and out.device == like.device and tuple(out.shape) == tuple(shape), (out.shape, out.dtype, shape, dtype)
+    assert is_cl(out) if cl else out.is_contiguous(), "out must be dense in the kernel's layout"
+    return out
+
+
+def affine_act_fwd(x, scale, shift, residual=None, relu=True, out=None):
     """act(x * scale[c] + shift[c] (+ residual)) on a dense fp32 NCHW tensor, one pass (stylex_affine_act_nchw_fwd)."""
     lib = _ensure_device(x)
     b, c, h, w = _dense_f32(x).shape
-    y = torch.empty_like(x)
+    y = _out_as(out, x.shape, torch.float32, x)
     _check(lib.stylex_affine_act_nchw_fwd(_ptr(x), _ptr(scale), _ptr(shift), _ptr(_dense_f32(residual)) if residual is not None
                                           else None, _ptr(y), b, c, h * w, int(relu), _stream()), "stylex_affine_act_nchw_fwd")
     return y
 
 
-def affine_act_bwd(gy, y, scale, relu=True, want_res=False):
+def affine_act_bwd(gy, y, scale, relu=True, want_res=False, out=None, out_res=None):
     lib = _ensure_device(gy)
     b, c, h, w = _dense_f32(gy).shape
-    gx = torch.empty_like(gy)
-    gres = torch.empty_like(gy) if want_res else None
+    gx = _out_as(out, gy.shape, torch.float32, gy)
+    gres = _out_as(out_res, gy.shape, torch.float32, gy) if want_res else None
     _check(lib.stylex_affine_act_nchw_bwd(_ptr(gy), _ptr(y) if relu else None, _ptr(scale), _ptr(gx),
                                           _ptr(gres) if want_res else None, b, c, h * w, int(relu), _stream()),
            "stylex_affine_act_nchw_bwd")
@@ -1081,43 +1091,43 @@ def softmax_ce_bwd(logits, targets, gloss):
     return g
 
 
-def affine_relu_maxpool_fwd(x, scale, shift, want_idx):
+def affine_relu_maxpool_fwd(x, scale, shift, want_idx, out=None, out_idx=None):
     lib = _ensure_device(x)
     b, c, h, w = _dense_f32(x).shape
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    y = torch.empty((b, c, ho, wo), dtype=torch.float32, device=x.device)
-    idx = torch.empty((b, c, ho, wo), dtype=torch.uint8, device=x.device) if want_idx else None
+    y = _out_as(out, (b, c, ho, wo), torch.float32, x)
+    idx = _out_as(out_idx, (b, c, ho, wo), torch.uint8, x) if want_idx else None
     _check(lib.stylex_affine_relu_maxpool_fwd(_ptr(x), _ptr(scale), _ptr(shift), _ptr(y), _ptr(idx) if want_idx else None,
                                               b, c, h, w, _stream()), "stylex_affine_relu_maxpool_fwd")
     return y, idx
 
 
-def affine_relu_maxpool_bwd(gy, idx, scale, in_hw):
+def affine_relu_maxpool_bwd(gy, idx, scale, in_hw, out=None):
     lib = _ensure_device(gy)
     b, c = _dense_f32(gy).shape[:2]
-    gx = torch.empty((b, c, in_hw[0], in_hw[1]), dtype=torch.float32, device=gy.device)
+    gx = _out_as(out, (b, c, int(in_hw[0]), int(in_hw[1])), torch.float32, gy)
     _check(lib.stylex_affine_relu_maxpool_bwd(_ptr(gy), _ptr(idx), _ptr(scale), _ptr(gx), b, c, in_hw[0], in_hw[1], _stream()),
            "stylex_affine_relu_maxpool_bwd")
     return gx
 
 
-def resize_norm_fwd(x, size, mean=None, std=None):
+def resize_norm_fwd(x, size, mean=None, std=None, out=None):
     """bilinear resize (align_corners=False) of a [B, C, H, W] fp32 tensor of ANY layout to `size`, then (. - mean[c]) / std[c]
     (both or neither given): dense NCHW fp32 result (stylex_resize_norm_fwd)."""
     lib = _ensure_device(x)
     assert x.dtype == torch.float32 and x.dim() == 4
     b, c, h, w = x.shape
-    y = torch.empty((b, c, int(size[0]), int(size[1])), dtype=torch.float32, device=x.device)
+    y = _out_as(out, (b, c, int(size[0]), int(size[1])), torch.float32, x)
     _check(lib.stylex_resize_norm_fwd(_ptr(x), _ptr(y), _ptr(mean), _ptr(std), _shape(b, c, h, w, int(size[0]), int(size[1])),
                                       _shape(*x.stride()), _stream()), "stylex_resize_norm_fwd")
     return y
 
 
-def resize_norm_bwd(gy, in_hw, std=None):
+def resize_norm_bwd(gy, in_hw, std=None, out=None):
     lib = _ensure_device(gy)
     gy = _dense_f32(gy.contiguous())
     b, c, ho, wo = gy.shape
-    gx = torch.empty((b, c, int(in_hw[0]), int(in_hw[1])), dtype=torch.float32, device=gy.device)
+    gx = _out_as(out, (b, c, int(in_hw[0]), int(in_hw[1])), torch.float32, gy)
     _check(lib.stylex_resize_norm_bwd(_ptr(gy), _ptr(gx), _ptr(std), _shape(b, c, int(in_hw[0]), int(in_hw[1]), ho, wo), _stream()),
            "stylex_resize_norm_bwd")
     return gx
@@ -1162,61 +1172,64 @@ def fid_moments_acc(x, total, gram):
     return feat
 
 
-def relu_gate_add(a, b, y):
+def relu_gate_add(a, b, y, out=None):
     """(y > 0) ? a + b : 0 for bf16 channels_last tensors of one shape (b may be None), one pass (stylex_relu_gate_add)."""
     lib = _ensure_device(a)
     assert a.dtype == torch.bfloat16 and is_cl(a) and is_cl(y) and y.shape == a.shape and y.dtype == a.dtype
     assert b is None or (is_cl(b) and b.shape == a.shape and b.dtype == a.dtype)
-    out = torch.empty_like(a)
+    out = _out_as(out, a.shape, torch.bfloat16, a, cl=True, make=lambda: torch.empty_like(a))
     _check(lib.stylex_relu_gate_add(_ptr(a), _ptr(b), _ptr(y), _ptr(out), a.numel(), _stream()), "stylex_relu_gate_add")
     return out
 
 
-def maxpool3s2_cl_fwd(x):
+def maxpool3s2_cl_fwd(x, out=None, out_idx=None):
     """nn.MaxPool2d(3, 2) of a bf16 channels_last feature map (LPIPS-AlexNet's two pools): (y, idx) — idx one byte per element,
     the window position of the first maximum, for maxpool3s2_cl_bwd (stylex_maxpool3s2_nhwc_fwd)."""
     lib = _ensure_device(x)
     assert x.dtype == torch.bfloat16 and is_cl(x) and x.shape[1] % 8 == 0 and x.shape[2] >= 3 and x.shape[3] >= 3, (x.dtype, x.shape)
     b, c, h, w = x.shape
     ho, wo = (h - 3) // 2 + 1, (w - 3) // 2 + 1
-    y = _empty((b, c, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    idx = torch.empty((b, ho, wo, c), dtype=torch.uint8, device=x.device)
+    y = _out_as(out, (b, c, ho, wo), torch.bfloat16, x, cl=True,
+                make=lambda: _empty((b, c, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last))
+    idx = _out_as(out_idx, (b, ho, wo, c), torch.uint8, x)
     _check(lib.stylex_maxpool3s2_nhwc_fwd(_ptr(x), _ptr(y), _ptr(idx), _shape(b, h, w, c), _stream()), "stylex_maxpool3s2_nhwc_fwd")
     return y, idx
 
 
-def maxpool3s2_cl_bwd(gy, idx, in_hw):
+def maxpool3s2_cl_bwd(gy, idx, in_hw, out=None):
     """Gradient of maxpool3s2_cl_fwd for an input of height / width `in_hw` (stylex_maxpool3s2_nhwc_bwd)."""
     lib = _ensure_device(gy)
     assert gy.dtype == torch.bfloat16 and is_cl(gy) and idx.dtype == torch.uint8
     b, c, ho, wo = gy.shape
     h, w = int(in_hw[0]), int(in_hw[1])
     assert tuple(idx.shape) == (b, ho, wo, c) and ho == (h - 3) // 2 + 1 and wo == (w - 3) // 2 + 1
-    gx = _empty((b, c, h, w), dtype=torch.bfloat16, device=gy.device, memory_format=torch.channels_last)
+    gx = _out_as(out, (b, c, h, w), torch.bfloat16, gy, cl=True,
+                 make=lambda: _empty((b, c, h, w), dtype=torch.bfloat16, device=gy.device, memory_format=torch.channels_last))
     _check(lib.stylex_maxpool3s2_nhwc_bwd(_ptr(gy), _ptr(idx), _ptr(gx), _shape(b, h, w, c), _stream()), "stylex_maxpool3s2_nhwc_bwd")
     return gx
 
 
-def nchw_to_cl_bf16(x, relu=False):
+def nchw_to_cl_bf16(x, relu=False, out=None):
     """Dense fp32 NCHW -> bf16 channels_last (optionally through a ReLU) in one pass (stylex_nchw_f32_to_nhwc_bf16)."""
     lib = _ensure_device(x)
     b, c, h, w = _dense_f32(x).shape
-    y = torch.empty((b, c, h, w), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    y = _out_as(out, (b, c, h, w), torch.bfloat16, x, cl=True,
+                make=lambda: torch.empty((b, c, h, w), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last))
     _check(lib.stylex_nchw_f32_to_nhwc_bf16(_ptr(x), _ptr(y), b, c, h * w, int(relu), _stream()), "stylex_nchw_f32_to_nhwc_bf16")
     return y
 
 
-def cl_bf16_to_nchw(g, gate=None):
+def cl_bf16_to_nchw(g, gate=None, out=None):
     """bf16 channels_last -> dense fp32 NCHW, optionally gated by (gate > 0) (stylex_nhwc_bf16_to_nchw_f32)."""
     lib = _ensure_device(g)
     assert is_cl(g) and g.dtype == torch.bfloat16 and (gate is None or (is_cl(gate) and gate.dtype == torch.bfloat16 and gate.shape == g.shape))
     b, c, h, w = g.shape
-    out = torch.empty((b, c, h, w), dtype=torch.float32, device=g.device)
+    out = _out_as(out, (b, c, h, w), torch.float32, g)
     _check(lib.stylex_nhwc_bf16_to_nchw_f32(_ptr(g), _ptr(gate), _ptr(out), b, c, h * w, _stream()), "stylex_nhwc_bf16_to_nchw_f32")
     return out
 
 
-def conv_image_grad(gy, w, in_hw, stride, pad):
+def conv_image_grad(gy, w, in_hw, stride, pad, out=None):
     """Input gradient of a K x K / stride-S convolution over a <= 4-channel image (the stems of the frozen classifier and of
     LPIPS-AlexNet), dense fp32 NCHW: gy [B, N, Ho, Wo], w [N, C, K, K] -> [B, C, Hi, Wi] (stylex_conv_image_grad)."""
     lib = _ensure_device(gy)
@@ -1224,13 +1237,14 @@ def conv_image_grad(gy, w, in_hw, stride, pad):
     assert gy.dtype == torch.float32 and w.dtype == torch.float32 and w.shape[2] == w.shape[3] and gy.shape[1] == w.shape[0]
     b, n, ho, wo = gy.shape
     c, k = int(w.shape[1]), int(w.shape[2])
-    dx = _empty((b, c, int(in_hw[0]), int(in_hw[1])), dtype=torch.float32, device=gy.device)
+    dx = _out_as(out, (b, c, int(in_hw[0]), int(in_hw[1])), torch.float32, gy,
+                 make=lambda: _empty((b, c, int(in_hw[0]), int(in_hw[1])), dtype=torch.float32, device=gy.device))
     _check(lib.stylex_conv_image_grad(_ptr(gy), _ptr(w), _ptr(dx), _shape(b, n, ho, wo, c, k, int(stride), int(pad), int(in_hw[0]),
                                                                          int(in_hw[1])), _stream()), "stylex_conv_image_grad")
     return dx
 
 
-def lpips_taps_fwd(f0s, f1s, lins, keep_norms):
+def lpips_taps_fwd(f0s, f1s, lins, keep_norms, out_norms=None):
     """sum over the taps of mean_p sum_c lin[c] (n0 - n1)^2  ->  ([B] distances, saved per-pixel norms)."""
     lib = _ensure_device(f0s[0])
     b = f0s[0].shape[0]
@@ -1240,8 +1254,9 @@ def lpips_taps_fwd(f0s, f1s, lins, keep_norms):
     for f0, f1, lin, nb in zip(f0s, f1s, lins, blocks):
         _, c, h, w = _dense_f32(f0).shape
         assert _dense_f32(f1).shape == f0.shape and lin.numel() == c
-        r0 = torch.empty((b, h * w), dtype=torch.float32, device=f0.device) if keep_norms else None
-        r1 = torch.empty_like(r0) if keep_norms else None
+        r0, r1 = out_norms[len(norms)] if out_norms is not None else (None, None)
+        r0 = _out_as(r0, (b, h * w), torch.float32, f0) if keep_norms else None
+        r1 = _out_as(r1, (b, h * w), torch.float32, f0) if keep_norms else None
         _check(lib.stylex_lpips_tap_fwd(_ptr(f0), _ptr(f1), _ptr(lin), ctypes.c_void_p(partial.data_ptr() + 4 * off), _ptr(r0),
                                         _ptr(r1), b, c, h * w, partial.shape[1], _stream()), "stylex_lpips_tap_fwd")
         norms.append((r0, r1))
@@ -1249,7 +1264,7 @@ def lpips_taps_fwd(f0s, f1s, lins, keep_norms):
     return partial.sum(dim=1), norms
 
 
-def lpips_taps_nhwc_fwd(f0s, f1s, lins, keep_norms):
+def lpips_taps_nhwc_fwd(f0s, f1s, lins, keep_norms, out_norms=None):
     """lpips_taps_fwd for bf16 channels_last feature maps (the taps of the bf16 LPIPS path)."""
     lib = _ensure_device(f0s[0])
     b = f0s[0].shape[0]
@@ -1259,8 +1274,9 @@ def lpips_taps_nhwc_fwd(f0s, f1s, lins, keep_norms):
     for f0, f1, lin, nb in zip(f0s, f1s, lins, blocks):
         _, c, h, w = f0.shape
         assert f1.shape == f0.shape and lin.numel() == c and is_cl(f0) and is_cl(f1) and f0.dtype == f1.dtype == torch.bfloat16
-        r0 = torch.empty((b, h * w), dtype=torch.float32, device=f0.device) if keep_norms else None
-        r1 = torch.empty_like(r0) if keep_norms else None
+        r0, r1 = out_norms[len(norms)] if out_norms is not None else (None, None)
+        r0 = _out_as(r0, (b, h * w), torch.float32, f0) if keep_norms else None
+        r1 = _out_as(r1, (b, h * w), torch.float32, f0) if keep_norms else None
         _check(lib.stylex_lpips_tap_nhwc_fwd(_ptr(f0), _ptr(f1), _ptr(lin), ctypes.c_void_p(partial.data_ptr() + 4 * off), _ptr(r0),
                                              _ptr(r1), b, c, h * w, partial.shape[1], _stream()), "stylex_lpips_tap_nhwc_fwd")
         norms.append((r0, r1))
@@ -1268,21 +1284,21 @@ def lpips_taps_nhwc_fwd(f0s, f1s, lins, keep_norms):
     return partial.sum(dim=1), norms
 
 
-def lpips_tap_nhwc_bwd(f0, f1, lin, r0, r1, gout, want0, want1):
+def lpips_tap_nhwc_bwd(f0, f1, lin, r0, r1, gout, want0, want1, out0=None, out1=None):
     lib = _ensure_device(f0)
     b, c, h, w = f0.shape
-    g0 = torch.empty_like(f0) if want0 else None  # (preserves channels_last)
-    g1 = torch.empty_like(f1) if want1 else None
+    g0 = _out_as(out0, f0.shape, torch.bfloat16, f0, cl=True, make=lambda: torch.empty_like(f0)) if want0 else None  # (channels_last)
+    g1 = _out_as(out1, f1.shape, torch.bfloat16, f1, cl=True, make=lambda: torch.empty_like(f1)) if want1 else None
     _check(lib.stylex_lpips_tap_nhwc_bwd(_ptr(f0), _ptr(f1), _ptr(lin), _ptr(r0), _ptr(r1), _ptr(gout), _ptr(g0), _ptr(g1), b, c, h * w,
                                          _stream()), "stylex_lpips_tap_nhwc_bwd")
     return g0, g1
 
 
-def lpips_tap_bwd(f0, f1, lin, r0, r1, gout, want0, want1):
+def lpips_tap_bwd(f0, f1, lin, r0, r1, gout, want0, want1, out0=None, out1=None):
     lib = _ensure_device(f0)
     b, c, h, w = f0.shape
-    g0 = torch.empty_like(f0) if want0 else None
-    g1 = torch.empty_like(f1) if want1 else None
+    g0 = _out_as(out0, f0.shape, torch.float32, f0, make=lambda: torch.empty_like(f0)) if want0 else None
+    g1 = _out_as(out1, f1.shape, torch.float32, f1, make=lambda: torch.empty_like(f1)) if want1 else None
     _check(lib.stylex_lpips_tap_bwd(_ptr(f0), _ptr(f1), _ptr(lin), _ptr(r0), _ptr(r1), _ptr(gout), _ptr(g0), _ptr(g1), b, c, h * w,
                                     _stream()), "stylex_lpips_tap_bwd")
     return g0, g1
