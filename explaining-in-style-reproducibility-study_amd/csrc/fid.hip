@@ -3,6 +3,7 @@
 //
 //   fid_prep_kernel          image batch -> Inception input: the byte an image file would hold, ToTensor's q / 255, the bilinear
 //                            resize to 299 x 299 (index rule of resize_norm_fwd_kernel, frozen_ew.hip) and 2 v - 1, one pass
+//   fid_prep_u8_kernel       the same from bytes (the output of the JPEG round trip, jpeg_rt.hip)
 //   affine_act_slice_kernel  the eval BatchNorm + ReLU tail of frozen_ew.hip with an output batch stride: the last layer of
 //                            an Inception branch writes its channel slice of the block's concatenated output (no torch.cat)
 //   fid_pool_kernel          f[b][d] = mean over the final map's pixels, fp32, index order (compensated sum)
@@ -66,6 +67,31 @@ __global__ __launch_bounds__(256) void fid_prep_kernel(const void* __restrict__ 
         const float r1 = w.l0 * p10 + w.l1 * p11;
         const float v = h.l0 * r0 + h.l1 * r1;
         y[i] = 2.f * v - 1.f;
+    }
+}
+
+// fid_prep_kernel reading bytes (dense [B][3][Hi][Wi], e.g. a decoded JPEG round trip, jpeg_rt.hip): q / 255 as the same
+// true division, the same blend with the same roundings — bit for bit fid_prep_kernel of the fp32 image q / 255
+__global__ __launch_bounds__(256) void fid_prep_u8_kernel(const unsigned char* __restrict__ x, float* __restrict__ y, int Hi, int Wi,
+                                                          int Ho, int Wo, unsigned total) {
+    const float rh = (float)Hi / Ho, rw = (float)Wi / Wo;
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        const int ox = i % Wo, oy = (i / Wo) % Ho, bc = i / (Wo * Ho);
+        const RsIdx h = rs_index(oy, rh, Hi), w = rs_index(ox, rw, Wi);
+        const unsigned char* p = x + (size_t)bc * Hi * Wi;
+        const float p00 = __fdiv_rn((float)p[h.i0 * Wi + w.i0], 255.f);
+        const float p01 = __fdiv_rn((float)p[h.i0 * Wi + w.i1], 255.f);
+        const float p10 = __fdiv_rn((float)p[h.i1 * Wi + w.i0], 255.f);
+        const float p11 = __fdiv_rn((float)p[h.i1 * Wi + w.i1], 255.f);
+        // the blend as the compiler contracts fid_prep_kernel's (one fma per sum, the second product rounded on its own),
+        // spelled out so that the two kernels cannot drift apart: tests/test_jpeg_gpu.py compares them bit for bit
+        {
+#pragma clang fp contract(off)
+            const float r0 = fmaf(w.l0, p00, w.l1 * p01);
+            const float r1 = fmaf(w.l0, p10, w.l1 * p11);
+            const float v = fmaf(h.l0, r0, h.l1 * r1);
+            y[i] = fmaf(v, 2.f, -1.f);
+        }
     }
 }
 
@@ -219,6 +245,18 @@ int stylex_fid_prep(const void* x, float* y, const int64_t* sh, const int64_t* s
         hipLaunchKernelGGL(fid_prep_kernel<false>, dim3(grid_for((unsigned long)total)), dim3(256), 0, (hipStream_t)stream, x, y,
                            (int)sh[1], (int)sh[2], (int)sh[3], (int)sh[4], (long)strides[0], (long)strides[1], (long)strides[2],
                            (long)strides[3], (unsigned)total);
+    return (int)hipGetLastError();
+}
+
+int stylex_fid_prep_u8(const unsigned char* x_u8, float* y, const int64_t* sh, void* stream) {
+    // sh = {B, Hi, Wi, Ho, Wo}; x_u8 dense [B][3][Hi][Wi]; y dense [B][3][Ho][Wo]
+    if (!x_u8 || !y || !sh) return STYLEX_EINVAL;
+    for (int k = 0; k < 5; ++k)
+        if (sh[k] < 1 || sh[k] > 0x7fffffffLL) return STYLEX_EINVAL;
+    const int64_t total = sh[0] * 3 * sh[3] * sh[4];
+    if (total > 0x7fffffffLL || sh[0] * 3 * sh[1] * sh[2] > 0x7fffffffLL) return STYLEX_EINVAL;
+    hipLaunchKernelGGL(fid_prep_u8_kernel, dim3(grid_for((unsigned long)total)), dim3(256), 0, (hipStream_t)stream, x_u8, y, (int)sh[1],
+                       (int)sh[2], (int)sh[3], (int)sh[4], (unsigned)total);
     return (int)hipGetLastError();
 }
 

@@ -44,6 +44,7 @@ DEFAULTS = dict(
     # MI355X additions
     precision="fp32",
     fid_weights=None,  # Inception weights of --calculate_fid_every: a path or random:<seed> (fid_inception.resolve_weights)
+    fid_jpeg=False,  # generated images of calculate_fid through the reference's JPEG round trip (quality 75) on the device
 )
 
 # train_from_folder kwarg -> Trainer kwarg, where the names differ

@@ -2,7 +2,8 @@
 and calls pytorch_fid on them): real and generated batches go from the loader / generator through ``stylex_fid_prep``,
 the Inception network (fid_inception.py) and ``stylex_fid_moments_acc`` without leaving the GPU; only the two raw moments
 (count, sum, upper triangle of the Gram matrix, fp64) come back to the host, where mean, covariance and the distance
-are computed in fp64.
+are computed in fp64.  The reference's generated images are .jpg files: ``add_fake(batch, jpeg_quality=75)`` applies that
+round trip on the device (``stylex_jpeg_roundtrip``) in front of the network.
 """
 import os
 
@@ -86,17 +87,23 @@ class FIDEvaluator:
         self.net, self.input_size = net, int(input_size)
         self.real = self.fake = None
 
-    def features(self, batch):
-        """Image batch [B, >= 3, H, W] in [0, 1] (fp32 or bf16, any layout) -> the network's last feature map."""
+    def features(self, batch, jpeg_quality=None):
+        """Image batch [B, >= 3, H, W] in [0, 1] (fp32 or bf16, any layout) -> the network's last feature map.  With
+        `jpeg_quality` the images first go through the JPEG round trip an image folder of .jpg files applies (the decoded
+        bytes of hip_backend.jpeg_roundtrip); None keeps the lossless (PNG) path."""
         import hip_backend as hb
 
         with torch.no_grad():
-            fm = self.net(hb.fid_prep(batch, self.input_size))
+            if jpeg_quality is None:
+                prepared = hb.fid_prep(batch, self.input_size)
+            else:
+                prepared = hb.fid_prep_u8(hb.jpeg_roundtrip(batch, int(jpeg_quality)), self.input_size)
+            fm = self.net(prepared)
         assert fm.dim() == 4 and fm.dtype == torch.float32, (tuple(fm.shape), fm.dtype)
         return fm
 
-    def _add(self, stats, batch):
-        fm = self.features(batch)
+    def _add(self, stats, batch, jpeg_quality=None):
+        fm = self.features(batch, jpeg_quality)
         if stats is None:
             stats = FIDStats(fm.shape[1], fm.device)
         stats.update(fm)
@@ -105,8 +112,8 @@ class FIDEvaluator:
     def add_real(self, batch):
         self.real = self._add(self.real, batch)
 
-    def add_fake(self, batch):
-        self.fake = self._add(self.fake, batch)
+    def add_fake(self, batch, jpeg_quality=None):
+        self.fake = self._add(self.fake, batch, jpeg_quality)
 
     def value(self):
         assert self.real is not None and self.fake is not None, "add_real and add_fake first"

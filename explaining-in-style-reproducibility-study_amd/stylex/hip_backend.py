@@ -131,6 +131,10 @@ SIGNATURES = {
                                                         ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "stylex_fid_moments_acc": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_void_p]),
+    "stylex_jpeg_roundtrip_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "stylex_jpeg_roundtrip": (ctypes.c_int, [_c_f, _c_f, _i64p, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_void_p]),
+    "stylex_fid_prep_u8": (ctypes.c_int, [_c_f, _c_f, _i64p, ctypes.c_void_p]),
     "stylex_bn_train_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     "stylex_bn_stats_nchw": (ctypes.c_int, [_c_f] * 5 + [ctypes.c_double, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -1142,6 +1146,34 @@ def fid_prep(x, size=299):
     y = torch.empty((b, 3, int(size), int(size)), dtype=torch.float32, device=x.device)
     _check(lib.stylex_fid_prep(_ptr(x), _ptr(y), _shape(b, h, w, int(size), int(size)), _shape(*x.stride()),
                                int(x.dtype == torch.bfloat16), _stream()), "stylex_fid_prep")
+    return y
+
+
+def jpeg_roundtrip(x, quality=75, out=None):
+    """Image batch [B, >= 3, H, W] (fp32 or bf16, any strides; H, W >= 8) -> uint8 [B, 3, H, W]: the bytes Pillow decodes from
+    the JPEG file save_image writes of each image at `quality` (4:2:0, libjpeg-turbo), computed on the device without a
+    file (stylex_jpeg_roundtrip).  `out`: a dense uint8 tensor of that shape to write (a view at any offset)."""
+    lib = _ensure_device(x)
+    assert x.dim() == 4 and x.shape[1] >= 3 and x.dtype in (torch.float32, torch.bfloat16)
+    b, _, h, w = x.shape
+    need = lib.stylex_jpeg_roundtrip_workspace_bytes(b, h, w)
+    if need < 0:
+        raise StylexHipError("stylex_jpeg_roundtrip: unsupported shape %s (H and W must be at least 8)" % (tuple(x.shape),))
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    y = _out_as(out, (b, 3, h, w), torch.uint8, x)
+    _check(lib.stylex_jpeg_roundtrip(_ptr(x), _ptr(y), _shape(b, h, w), _shape(*x.stride()), int(x.dtype == torch.bfloat16),
+                                     int(quality), _ptr(ws), need, _stream()), "stylex_jpeg_roundtrip")
+    return y
+
+
+def fid_prep_u8(x, size=299):
+    """Dense uint8 batch [B, 3, H, W] -> Inception input [B, 3, size, size], dense fp32: fid_prep of the image x / 255, bit for
+    bit (stylex_fid_prep_u8)."""
+    lib = _ensure_device(x)
+    assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.uint8 and x.is_contiguous()
+    b, _, h, w = x.shape
+    y = torch.empty((b, 3, int(size), int(size)), dtype=torch.float32, device=x.device)
+    _check(lib.stylex_fid_prep_u8(_ptr(x), _ptr(y), _shape(b, h, w, int(size), int(size)), _stream()), "stylex_fid_prep_u8")
     return y
 
 

@@ -652,7 +652,7 @@ class Trainer:
                  # --- extensions (defaults reproduce the reference) ---
                  classifier=None, lpips_fn=None, gp_every=4, pl_every=32, pl_after=5000, device=None,
                  save_training_state=False, graphs=None, graph_warmup=4, new_architecture=False, device_pipeline=None,
-                 device_rng=None, fid_weights=None, *args, **kwargs):
+                 device_rng=None, fid_weights=None, fid_jpeg=False, *args, **kwargs):
         kl_rec_during_disc = kwargs.pop("kl_rec_during_disc", False)  # cli.py forwards it; only the new architecture reads it
         # new_architecture = the conditional-D variant the reference ships as stylex_train_new.py (cli.py:17-22)
         self.new_architecture = bool(new_architecture)
@@ -720,6 +720,9 @@ class Trainer:
         # Inception weights of calculate_fid: a path, "random:<seed>" (tests, timing) or None = $STYLEX_FID_WEIGHTS, then
         # torch hub's checkpoint folder (fid_inception.resolve_weights); read at the first FID step
         self.fid_weights, self._fid_eval = fid_weights, None
+        # fid_jpeg: the generated images of calculate_fid go through the JPEG round trip of the reference's .jpg files
+        # (quality 75) on the device; nothing changes for transparent models, whose image_extension is png
+        self.fid_jpeg = bool(fid_jpeg)
         self.is_ddp, self.is_main, self.rank, self.world_size = is_ddp, rank == 0, rank, world_size
         self.sample_from_encoder = sample_from_encoder
         self.logger = None
@@ -1605,7 +1608,11 @@ class Trainer:
         image file applies, resize to 299 px), the FID Inception-v3 and the fp64 moments kernel on the GPU (fid.py).  The
         real statistics are kept in fid_dir/real_stats.npz, as the reference keeps its folder of real images: reused unless
         clear_fid_cache is set or they were made at another image size / with other Inception weights.  Rank 0 only.
-        Not the reference's: generated images are quantised to 8 bits but not JPEG-compressed (image_extension)."""
+        The reference saves the generated images with image_extension, .jpg for opaque models (Pillow: quality 75,
+        4:2:0), and the reals as PNG.  With fid_jpeg=True the generated batches go through that JPEG round trip on the
+        device (hip_backend.jpeg_roundtrip: the bytes Pillow would decode, no file) — the setting whose numbers compare
+        with the reference's fid_scores.txt; the reals and transparent models (.png) stay lossless.  With the default
+        fid_jpeg=False the generated images are quantised to 8 bits only."""
         if not self.is_main:
             return None
         import fid
@@ -1623,6 +1630,7 @@ class Trainer:
                 ev.add_real(self._next_batch())
             ev.real.save(cache, tag)
         ev.fake = None
+        jpeg_quality = 75 if self.fid_jpeg and self.image_extension == "jpg" else None  # Pillow's default quality
         m.eval()
         for _ in range(num_batches):
             latents = noise_list(self.batch_size, m.G.num_layers, self._z_dim, device=self.device)
@@ -1633,7 +1641,8 @@ class Trainer:
                 # generate_truncated (:1741-1745) cannot concatenate: drawn as evaluate draws them (:1618-1620)
                 probs = torch.rand(self.batch_size, 2, device=self.device)
                 probs = probs / torch.sum(probs, dim=1, keepdim=True)
-            ev.add_fake(self.generate_truncated(m.SE, m.GE, latents, n, trunc_psi=self.trunc_psi, probabilities=probs))
+            ev.add_fake(self.generate_truncated(m.SE, m.GE, latents, n, trunc_psi=self.trunc_psi, probabilities=probs),
+                        jpeg_quality=jpeg_quality)
         return ev.value()
 
     @torch.no_grad()

@@ -321,6 +321,26 @@ int stylex_affine_act_nchw_slice_fwd(const float* x, const float* scale, const f
                                      int64_t B, int64_t C, int64_t HW, int64_t y_batch_stride, int relu, void* stream);
 int stylex_fid_moments_acc(const float* x, float* feat, double* sum, double* gram, int64_t B, int64_t D, int64_t HW, void* stream);
 
+/* ---- JPEG round trip on the device (csrc/jpeg_rt.hip) ---------------------------------------------------------
+ * The reference saves the generated images of calculate_fid as JPEG files (Pillow: quality 75, 4:2:0) and pytorch_fid
+ * decodes them.  stylex_jpeg_roundtrip gives the decoded bytes without a file: per image the byte of stylex_fid_prep
+ * (floor(clamp(x * 255 + 0.5, 0, 255))), then what libjpeg-turbo decodes (fancy upsampling) from the baseline JPEG it
+ * writes of those bytes at `quality` (standard tables, 4:2:0, JDCT_ISLOW) — colour conversion, edge replication, 2 x 2
+ * chroma downsampling, 8 x 8 integer DCT, quantisation and their inverses, all in 32-bit integers; the entropy coder is
+ * lossless and left out.  sh = {B, H, W}; x [B][>= 3][H][W], fp32 or bf16 (x_is_bf16), read through its element strides
+ * {b, c, h, w} (non-negative; any layout), channels 0..2; y_u8 dense uint8 [B][3][H][W].  workspace: at least
+ * stylex_jpeg_roundtrip_workspace_bytes(B, H, W) bytes, 16-byte aligned (the decoded Y, Cb, Cr planes padded to whole
+ * 16 x 16 MCUs).  Two launches whatever B is; no atomics: the same input gives the same bytes.
+ * STYLEX_EINVAL: a NULL pointer, quality outside 1..100, H or W below 8 (smaller planes take other upsampling paths in
+ * libjpeg), a workspace that is too small or misaligned, offsets past 2^31.  workspace_bytes returns -1 for such a shape.
+ *
+ * stylex_fid_prep_u8: stylex_fid_prep of a dense uint8 batch [B][3][Hi][Wi] (sh = {B, Hi, Wi, Ho, Wo}): q / 255 (a true
+ *   division), the same bilinear resize, 2 v - 1; bit for bit stylex_fid_prep of the fp32 image q / 255. */
+int64_t stylex_jpeg_roundtrip_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int stylex_jpeg_roundtrip(const void* x, unsigned char* y_u8, const int64_t* sh, const int64_t* strides, int x_is_bf16, int quality,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+int stylex_fid_prep_u8(const unsigned char* x_u8, float* y, const int64_t* sh, void* stream);
+
 /* ---- layout bridges: the library's dense fp32 NCHW tensors <-> this library's bf16 NHWC tensors (round 6) -------------
  * Where a frozen network keeps part of its path on the library's fp32 convolutions (the classifier forward, north_star; the
  * LPIPS stem) and the rest runs on the bf16 kernels: frozen_resnet._ResNetBodyHybrid, lpips_alex._taps_bf16.  C % 8 == 0.

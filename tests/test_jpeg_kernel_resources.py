@@ -1,0 +1,51 @@
+"""Build hygiene of the JPEG round-trip kernels (csrc/jpeg_rt.hip) and of the byte-reading FID prep kernel (csrc/fid.hip): no
+scratch memory and no spilled VGPRs — the codec kernel keeps an 8-point line in registers through the column transform,
+quantisation and the inverse column transform, and its quantisation tables arrive as a kernel argument that must be read
+in place.  Compiled with the Makefile's flags for each file; same hipcc remarks and parsing as
+tests/test_fid_kernel_resources.py."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "explaining-in-style-reproducibility-study_amd", "csrc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+KERNELS = {"jpeg_rt": ["jpeg_codec_kernelILb0", "jpeg_codec_kernelILb1", "jpeg_upsample_rgb_kernelILb0",
+                       "jpeg_upsample_rgb_kernelILb1"],
+           "fid": ["fid_prep_u8_kernel"]}
+
+
+def _makefile_flags(stem):
+    for line in open(os.path.join(CSRC, "Makefile")):
+        m = re.match(r"CXXFLAGS_%s\s*=\s*(.*)" % re.escape(stem), line)
+        if m:
+            return m.group(1).split()
+    return []
+
+
+@pytest.mark.skipif(not os.path.isfile(HIPCC), reason="needs hipcc")
+@pytest.mark.parametrize("stem", sorted(KERNELS))
+def test_jpeg_kernels_use_no_scratch(tmp_path, stem):
+    assert "-fno-slp-vectorize" in _makefile_flags(stem)
+    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function"]
+                         + _makefile_flags(stem) + ["-Rpass-analysis=kernel-resource-usage", "-c",
+                                                    os.path.join(CSRC, stem + ".hip"), "-o", str(tmp_path / "k.o")],
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    seen = {}
+    for blk in re.split(r"remark: Function Name: ", out.stderr)[1:]:
+        name = blk.split()[0]
+        scratch = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blk)
+        spill = re.search(r"VGPRs Spill: (\d+)", blk)
+        vgprs = re.search(r" VGPRs: (\d+)", blk)
+        seen[name] = (int(scratch.group(1)) if scratch else None, int(spill.group(1)) if spill else None)
+        print(name, "VGPRs", vgprs.group(1) if vgprs else "?", "scratch", seen[name][0])
+    for k in KERNELS[stem]:
+        hits = {n: v for n, v in seen.items() if k in n}
+        assert hits, (k, sorted(seen))
+        for n, (scratch, spill) in hits.items():
+            assert scratch == 0 and spill == 0, (n, "scratch bytes/lane", scratch, "spilled VGPRs", spill)
