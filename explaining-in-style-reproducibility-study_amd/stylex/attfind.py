@@ -32,6 +32,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+import ops
+
 DATASETS = ("style_change", "latents", "base_prob", "minima", "maxima", "style_coordinates", "original_images",
             "noise", "discriminator")
 
@@ -397,3 +399,204 @@ def visualize_style_by_distance_in_s(G, classifier, all_dlatents, all_style_vect
                                         style_min[sindex], style_max[sindex], shift_size, noise, class_index)
     rows = [pair_image(base[i], changed[i]) for i in range(len(idx))]
     return np.concatenate(rows[:max_images], axis=0) if len(rows) >= 3 else np.array([])
+
+
+# ---- the counterfactual experiment (stylex/FID_TensorFlow.ipynb cells 9, 12, 13, 20, 24, 25) --------------------
+
+
+def rank_class_directions(style_change_effect, base_probs, num_indices=10, effect_threshold=0.2):
+    """Cell 13 of FID_TensorFlow.ipynb on an (already filtered) effect tensor [images, 2, coords, 2]: per class c the greedy
+    selection over the images of the OTHER class (``max_image_effect = 5 * effect_threshold``), the two selections joined
+    into one list of (direction, coordinate) "for moving class 1 to class 0" — class 1's entries with the direction
+    swapped, minus the coordinates class 0 selected, then class 0's — and sorted by descending
+    ``mean(effect[:, d, s, 0]) + mean(effect[:, 1 - d, s, 1])`` over all images.  The list can be longer than `num_indices`
+    and can hold a coordinate once per direction; the counterfactual sweep takes its first k entries."""
+    effect = np.asarray(style_change_effect)
+    if effect.ndim != 4 or effect.shape[-1] != 2 or effect.shape[1] != 2:
+        raise ValueError("rank_class_directions needs a binary effect tensor [images, 2, coords, 2], got %s" % (effect.shape,))
+    labels = np.argmax(np.asarray(base_probs), axis=1)
+    members = {c: np.nonzero(labels == c)[0] for c in (0, 1)}
+    for c in (0, 1):
+        if members[c].size == 0:
+            raise ValueError("rank_class_directions: no image of class %d" % c)
+    sel = {c: find_significant_styles(effect[members[1 - c]].astype(np.float64), num_indices, c,
+                                      max_image_effect=5 * effect_threshold) for c in (0, 1)}
+    taken = {s for _, s in sel[0]}
+    joined = [(1 - d, s) for d, s in sel[1] if s not in taken] + sel[0]
+    scores = [np.mean(effect[:, d, s, 0]) + np.mean(effect[:, 1 - d, s, 1]) for d, s in joined]
+    return [(int(joined[i][0]), int(joined[i][1])) for i in np.argsort(scores)[::-1]]
+
+
+def style_segments(G):
+    """[0, c1_0, c1_0 + f_0, ...]: where the blocks' style1 / style2 vectors start inside the style-coordinate vector."""
+    seg = [0]
+    for block in G.blocks:
+        seg += [seg[-1] + block.input_channels, seg[-1] + block.num_style_coords]
+    return seg
+
+
+def edited_styles(coords, edits, style_min, style_max, base_class, levels, seg_start, shift_size=1.0):
+    """Cell 20's edits for an image batch and every level at once: level k applies the first k (direction, coordinate)
+    pairs IN LIST ORDER, each ``s += (target - s) * shift_size`` on the value the earlier ones left (the notebook recomputes
+    the style vector after every bias mutation), target = the coordinate's minimum for direction 0 and maximum for 1, swapped
+    for an image of base class 0 (its ``flip``).  coords [n, S] fp32, base_class [n] int32; returns one dense
+    [levels, n, width] tensor per segment of `seg_start`.  One launch where the op surface has ``style_edit_levels``
+    (csrc/style_edit.hip); else — the CPU test double — the fp32 torch composition below, which is also the definition
+    the kernel is held to bit for bit."""
+    fused = getattr(ops.impl(), "style_edit_levels", None)
+    if fused is not None:
+        return fused(coords, style_min, style_max, [s for _, s in edits], [d for d, _ in edits], base_class, levels,
+                     seg_start, shift_size)
+    return edited_styles_composition(coords, edits, style_min, style_max, base_class, levels, seg_start, shift_size)
+
+
+def edited_styles_composition(coords, edits, style_min, style_max, base_class, levels, seg_start, shift_size=1.0):
+    """edited_styles as indexed fp32 torch updates, change_images' arithmetic per edit: K indexed updates per level and
+    one slice copy per segment."""
+    out = []
+    for k in levels:
+        s = coords.clone()
+        for d, c in edits[:k]:
+            towards_min = (base_class == 0) != (d == 0)
+            target = torch.where(towards_min, style_min[c], style_max[c])
+            delta = (target - s[:, c]) * shift_size
+            s[:, c] += delta
+        out.append(s)
+    out = torch.stack(out)
+    return [out[:, :, a:b].contiguous() for a, b in zip(seg_start, seg_start[1:])]
+
+
+def _rgb_style(block, istyle):
+    """The to-RGB style as the generator's own forward gets it: the third column block of the fused affine GEMM where that
+    runs (None: RGBBlock computes it itself) — so a block re-run with `styles=` overrides has the bits of the base pass."""
+    fused = ops.style_affines(istyle, block.to_style1, block.to_style2, block.to_rgb.to_style)
+    return None if fused is None else fused[2]
+
+
+def _run_blocks(G, first, x, rgb, w_tensor, noise, styles_of):
+    """Blocks first..L-1 as Generator.forward runs them (w_tensor [n, L, D]), every block on the overriding styles
+    styles_of(li)."""
+    per_layer = w_tensor.unbind(1)
+    for li in range(first, len(G.blocks)):
+        block, w = G.blocks[li], per_layer[li]
+        if li > first and G.attns[li] is not None:  # block `first`'s own attention is already in its input
+            x = G.attns[li](x)
+        x, _ = block.forward_main(x, w, noise, styles=styles_of(li))
+        rgb = block.to_rgb(x, rgb, w, style=_rgb_style(block, w), padded=True)
+    if rgb.shape[1] == 4 and G.blocks[0].to_rgb.conv.filters == 3:
+        rgb = rgb[:, :3]
+    return rgb.float()
+
+
+@torch.no_grad()
+def counterfactual_images(G, classifier, dlatents, edits, style_min, style_max, noise, levels, shift_size=1.0,
+                          image_batch=32, share_prefix=True):
+    """Cell 20 (``create_counterfactual_dataset``) batched: yields (level_k, images [n, 3, S, S] fp32, logits [n, C]) per
+    image batch and level — the image of every latent with the first level_k `edits` ((direction, coordinate) pairs, the
+    list of rank_class_directions) applied together, and the classifier's logits on it.  Per image batch one base pass
+    (``G(w, noise, get_style_coords=True)`` and the classifier: base_class = argmax, the notebook's
+    ``get_classifier_results``), one call for the edited styles of all levels (edited_styles), then the levels in the order
+    given.  Level k changes nothing before block m_k = the first block any of its k coordinates lives in: with
+    `share_prefix` the feature map and RGB entering block m_k come from the base pass and only blocks m_k..L-1 run, on
+    overriding styles; level 0 is the base image itself.  no_const and attn_layers: as in _prefix_states / _suffix (a style
+    bias does not enter the first activation; a block's attention is part of its stored input).  share_prefix=False runs
+    every block (the equality test, the timing record).  Memory is bounded by `image_batch`."""
+    dev = next(G.parameters()).device
+
+    def on_device(v):
+        return torch.as_tensor(v if isinstance(v, torch.Tensor) else np.asarray(v), dtype=torch.float32, device=dev)
+
+    w_all = on_device(dlatents)
+    edits = [(int(d), int(s)) for d, s in edits]
+    levels = [int(k) for k in levels]
+    if any(not 0 <= k <= len(edits) for k in levels):
+        raise ValueError("levels %s outside [0, %d]" % (levels, len(edits)))
+    smin, smax = on_device(style_min).reshape(-1).contiguous(), on_device(style_max).reshape(-1).contiguous()
+    noise = torch.as_tensor(noise).to(dev)
+    seg = style_segments(G)
+    first_block = [_block_of(G, s)[0] for _, s in edits]
+    for lo in range(0, w_all.shape[0], image_batch):
+        w = w_all[lo:lo + image_batch]
+        n = w.shape[0]
+        nz = noise.expand(n, -1, -1, -1)
+        states = []
+        w_tensor = styles_def_to_tensor([(w, G.num_layers)])
+        base_img, coords = G(w_tensor, nz, get_style_coords=True, block_inputs=states)
+        base_logits = classifier.classify_images(base_img)
+        coords = coords.float().contiguous()
+        if edits:
+            base_class = base_logits.argmax(dim=-1).to(torch.int32)
+            segs = edited_styles(coords, edits, smin, smax, base_class, levels, seg, shift_size)
+        else:  # nothing to apply: every level is a copy
+            segs = [coords[None, :, a:b].expand(len(levels), -1, -1).contiguous() for a, b in zip(seg, seg[1:])]
+        for row, k in enumerate(levels):
+            m = min(first_block[:k], default=len(G.blocks)) if share_prefix else 0
+            if m == len(G.blocks):
+                yield k, base_img, base_logits
+                continue
+            if share_prefix:
+                x, rgb = states[m]
+            else:
+                x, rgb = G.initial_conv(G.first_activation(w_tensor)), None
+                if G.attns[0] is not None:
+                    x = G.attns[0](x)
+            img = _run_blocks(G, m, x, rgb, w_tensor, nz, lambda li: (segs[2 * li][row], segs[2 * li + 1][row]))
+            yield k, img, classifier.classify_images(img)
+
+
+@torch.no_grad()
+def counterfactual_sweep(stylex, classifier, records, edits, num_attributes=10, shift_size=1.0, fid=None, image_batch=32):
+    """Cells 24 + 25's experiment (``fid_topk``) on AttFind records (``latents, minima, maxima, noise, original_images``):
+    for k = 1..K (K = `num_attributes`, at most len(edits)) the counterfactual image of every latent with the first k
+    `edits` applied, in one pass over the image batches (counterfactual_images, all levels per batch).  Returns
+    ``k`` [1..K], ``flips`` [K] (images whose classifier argmax differs from their base class; counted on the device, read
+    once at the end), ``flip_rate`` [K], ``base_class`` [N] and, with `fid` a fid.FIDEvaluator, ``fid`` [K + 1]:
+    FID(original_images, generated) then FID(original_images, counterfactual_k), ``fid_topk``'s order — the real moments
+    accumulated once, one FIDStats per level, every image through the lossless path (the notebook writes PNG files)."""
+    G = stylex.G
+    dev = next(G.parameters()).device
+    edits = [(int(d), int(s)) for d, s in edits]
+    top = min(int(num_attributes), len(edits))
+    if top < 1:
+        raise ValueError("counterfactual_sweep needs at least one edit and num_attributes >= 1")
+    latents = np.asarray(records["latents"])
+    n = latents.shape[0]
+    flips = torch.zeros(top, dtype=torch.int64, device=dev)
+    base_classes, stats = [], [None] * (top + 1)
+    if fid is not None:
+        from fid import FIDStats, frechet_distance
+
+        originals = torch.as_tensor(np.asarray(records["original_images"]), dtype=torch.float32)
+        fid.real = None
+        for lo in range(0, n, image_batch):
+            fid.add_real(originals[lo:lo + image_batch].to(dev))
+    base = None
+    for k, images, logits in counterfactual_images(G, classifier, latents, edits[:top], records["minima"], records["maxima"],
+                                                   records["noise"], list(range(top + 1)), shift_size=shift_size,
+                                                   image_batch=image_batch):
+        if k == 0:
+            base = logits.argmax(dim=-1)
+            base_classes.append(base)
+        else:
+            flips[k - 1] += (logits.argmax(dim=-1) != base).sum()
+        if fid is not None:
+            fm = fid.features(images)
+            if stats[k] is None:
+                stats[k] = FIDStats(fm.shape[1], fm.device)
+            stats[k].update(fm)
+    counts = [int(v) for v in flips.tolist()]
+    out = {"k": list(range(1, top + 1)), "flips": counts, "flip_rate": [c / n for c in counts],
+           "base_class": torch.cat(base_classes).cpu().numpy().astype(np.int64)}
+    if fid is not None:
+        real = fid.real.mean_cov()
+        out["fid"] = [frechet_distance(*real, *st.mean_cov()) for st in stats]
+    return out
+
+
+def write_fid_table(fids, path):
+    """Cell 25 (``save_fids``) without pandas: the one-row table ``DataFrame.to_csv`` writes — an empty index header, the
+    column names, then row 0 with every value formatted '.2f'."""
+    names = ["Original-Generated", "Original-Attribute 1"] + ["Original-Attributes 1-%d" % i for i in range(2, len(fids))]
+    with open(path, "w") as f:
+        f.write("," + ",".join(names[:len(fids)]) + "\n")
+        f.write("0," + ",".join(format(v, ".2f") for v in fids) + "\n")

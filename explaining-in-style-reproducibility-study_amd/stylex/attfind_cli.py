@@ -5,12 +5,19 @@ StyleSpace extraction on an image folder, and write the records, the selected co
     python attfind_cli.py --name <run> --models_dir <dir> --data <folder> [--new_architecture] [--load_from N]
         --num_images N [--shift_size 1] [--chunk 256] [--first_pass_batch 1]
         [--use_discriminator --discriminator_threshold X | --find_threshold] [--num_indices 5] [--multi_gpus] [--precision fp32]
+        [--counterfactual_fid K --fid_weights SPEC [--counterfactual_shift 1]]
 
 The model is built as ``cli.py --generate`` builds it (``Trainer.load`` reads ``<models_dir>/<name>/.config.json`` and
 the checkpoint), the classifier through the Trainer's ``classifier_name`` / ``classifier_path``.  Everything is written
 by rank 0 to ``<results_dir>/<name>/attfind``: ``discriminator_threshold.{hdf5|npz}`` with ``--find_threshold``, else
 ``style_change_records.{hdf5|npz}``, ``significant_styles.json`` (cells 14-16: ``find_significant_styles`` per class after
-``split_by_class``) and one ``visualize_style_by_distance_in_s`` PNG per selected coordinate (cell 23).
+``split_by_class``) and one ``visualize_style_by_distance_in_s`` PNG per selected coordinate (cell 23).  With
+``--counterfactual_fid K`` (default 0: off) rank 0 then runs the counterfactual experiment of the reference's
+``stylex/FID_TensorFlow.ipynb`` on the records: the attributes ranked across the two classes
+(``attfind.rank_class_directions``), the top-k changed together for k = 1..K (``attfind.counterfactual_sweep``),
+``counterfactual_fid.csv`` (the notebook's table: FID(original, generated), FID(original, counterfactual_k)) and
+``counterfactual.json`` (the ranked list, flip counts and rates, base classes).  ``--fid_weights`` names the Inception
+weights as ``Trainer(fid_weights=)`` does (``random:<seed>`` for tests).
 
 Multi-GPU: the sweep shards over images (attfind.py).  ``--multi_gpus`` starts one process per GPU (``--num_gpus N`` to
 use fewer); the parent counts the GPUs in a short-lived child process and spawns the ranks without ever touching the
@@ -35,7 +42,8 @@ DEFAULTS = dict(
     image_size=64, network_capacity=16, fmap_max=512, classifier_name="resnet", classifier_path="mobilenet-64px-gender.pth",
     num_images=10, shift_size=1.0, chunk=256, first_pass_batch=1, use_discriminator=False, discriminator_threshold=None,
     find_threshold=False, num_indices=5, max_image_effect=2.5, split_by_class=True, max_images=10, visualize_shift_size=2.0,
-    multi_gpus=False, num_gpus=None, seed=42, precision="fp32",
+    multi_gpus=False, num_gpus=None, seed=42, precision="fp32", counterfactual_fid=0, fid_weights=None,
+    counterfactual_shift=1.0,
 )
 
 
@@ -96,6 +104,26 @@ def select_and_visualize(a, model, records, folder):
     print("selected (direction, coordinate):", selection)
 
 
+def counterfactual_experiment(a, model, records, folder):
+    """FID_TensorFlow.ipynb cells 11 (filter_unstable_images, its defaults), 13, 20, 24 and 25 on the written records."""
+    import numpy as np
+
+    import fid
+    import fid_inception
+
+    effect = attfind.filter_unstable_images(np.array(records["style_change"], copy=True))
+    ranked = attfind.rank_class_directions(effect, records["base_prob"])
+    evaluator = fid.FIDEvaluator(fid_inception.build(a["fid_weights"], model.device))
+    out = attfind.counterfactual_sweep(model.StylEx, model.classifier, records, ranked, num_attributes=a["counterfactual_fid"],
+                                       shift_size=a["counterfactual_shift"], fid=evaluator)
+    attfind.write_fid_table(out["fid"], os.path.join(folder, "counterfactual_fid.csv"))
+    with open(os.path.join(folder, "counterfactual.json"), "w") as f:
+        json.dump(dict(ranked=[[d, s] for d, s in ranked], k=out["k"], flips=out["flips"], flip_rate=out["flip_rate"],
+                       base_class=[int(c) for c in out["base_class"]], shift_size=a["counterfactual_shift"]), f)
+    print("counterfactual FID (generated, top-1 .. top-%d):" % len(out["k"]), ["%.2f" % v for v in out["fid"]],
+          "flip rate:", out["flip_rate"])
+
+
 def run(rank, world_size, a, local_rank=None, spawned=True):
     on_gpu = torch.cuda.is_available()
     device_index = (rank if local_rank is None else local_rank) % max(1, torch.cuda.device_count()) if on_gpu else 0
@@ -130,7 +158,10 @@ def run(rank, world_size, a, local_rank=None, spawned=True):
                                    use_discriminator=a["use_discriminator"], chunk=a["chunk"],
                                    results_folder=folder if rank == 0 else None, first_pass_batch=a["first_pass_batch"])
         if rank == 0:
-            select_and_visualize(a, model, attfind.load_records(folder), folder)
+            records = attfind.load_records(folder)
+            select_and_visualize(a, model, records, folder)
+            if a["counterfactual_fid"] > 0:
+                counterfactual_experiment(a, model, records, folder)
     if world_size > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -210,6 +210,8 @@ SIGNATURES = {
                                                ctypes.c_void_p]),
     "stylex_crop_lut_u8": (ctypes.c_int, [ctypes.c_void_p, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_f,
                                           ctypes.c_int64, _c_f, _c_f, ctypes.c_int64, ctypes.c_void_p]),
+    "stylex_style_edit_max_k": (ctypes.c_int64, []),
+    "stylex_style_edit_levels": (ctypes.c_int, [_c_f] * 9 + [ctypes.c_int64] * 5 + [ctypes.c_float, ctypes.c_void_p]),
     "stylex_timing_report": (ctypes.c_int, [ctypes.c_int, _i64p, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }
@@ -1884,6 +1886,56 @@ def torgb_bwd(x, gy, s1, w, want_gx=True):
     _check(lib.stylex_torgb_bwd(_ptr(x), _ptr(gy), _ptr(s1), _ptr(w), _ptr(gx), _ptr(partial), shp, _stream()),
            "stylex_torgb_bwd")
     return gx, (partial.sum(dim=1) if nch > 1 else partial[:, 0])
+
+
+_STYLE_EDIT_MAX_K = None
+
+
+def style_edit_max_k():
+    """Longest edit list of stylex_style_edit_levels."""
+    global _STYLE_EDIT_MAX_K
+    if _STYLE_EDIT_MAX_K is None:
+        _STYLE_EDIT_MAX_K = int(load_library().stylex_style_edit_max_k())
+    return _STYLE_EDIT_MAX_K
+
+
+def _host_i32(values, what):
+    v = [int(i) for i in values]
+    if not v:
+        raise ValueError("style_edit_levels: %s is empty" % what)
+    return v
+
+
+def style_edit_levels(coords, smin, smax, sindex, direction, base_class, level_k, seg_start, shift_size, out=None):
+    """The edited style vectors of the counterfactual experiment, one launch (stylex_style_edit_levels).  coords [N, S],
+    smin / smax [S] fp32 and base_class [N] on the device; sindex, direction [K], level_k [L] and seg_start [G + 1] host
+    sequences of ints, checked here (the device cannot report them): 0 <= sindex < S, direction in {0, 1}, 0 <= level_k <= K,
+    seg_start[0] = 0 < ... < seg_start[G] = S.  Level l applies the first level_k[l] (direction, sindex) pairs in list order;
+    base_class 0 swaps every direction.  Returns the G segments as dense [L, N, w_g] tensors, views of one buffer of
+    L * N * S floats (`out`: a dense fp32 tensor of that many elements to write instead of a new one)."""
+    n, s = _dense_f32(coords).shape
+    sindex, direction = _host_i32(sindex, "sindex"), _host_i32(direction, "direction")
+    level_k, seg_start = _host_i32(level_k, "level_k"), _host_i32(seg_start, "seg_start")
+    k, nl, g = len(sindex), len(level_k), len(seg_start) - 1
+    if len(direction) != k or k > style_edit_max_k():
+        raise ValueError("style_edit_levels: %d coordinates, %d directions (at most %d edits)" % (k, len(direction), style_edit_max_k()))
+    if any(not 0 <= i < s for i in sindex) or any(d not in (0, 1) for d in direction):
+        raise ValueError("style_edit_levels: a coordinate outside [0, %d) or a direction outside {0, 1}" % s)
+    if any(not 0 <= v <= k for v in level_k):
+        raise ValueError("style_edit_levels: a level outside [0, %d]" % k)
+    if g < 1 or seg_start[0] != 0 or seg_start[-1] != s or any(b <= a for a, b in zip(seg_start, seg_start[1:])):
+        raise ValueError("style_edit_levels: seg_start must rise strictly from 0 to %d" % s)
+    lib = _ensure_device(coords)
+    smin, smax = _dense_f32(smin), _dense_f32(smax)
+    assert smin.numel() == s and smax.numel() == s and smin.device == coords.device == smax.device
+    assert base_class.dtype == torch.int32 and base_class.is_contiguous() and base_class.numel() == n
+    assert base_class.device == coords.device
+    table = torch.tensor(sindex + direction + level_k + seg_start, dtype=torch.int32).to(coords.device, non_blocking=True)
+    flat = _out_as(out, (nl * n * s,), torch.float32, coords)
+    _check(lib.stylex_style_edit_levels(_ptr(coords), _ptr(smin), _ptr(smax), _ptr(table), _ptr(table[k:]), _ptr(base_class),
+                                        _ptr(table[2 * k:]), _ptr(table[2 * k + nl:]), _ptr(flat), n, s, k, nl, g,
+                                        float(shift_size), _stream()), "stylex_style_edit_levels")
+    return [flat[nl * n * a:nl * n * b].view(nl, n, b - a) for a, b in zip(seg_start, seg_start[1:])]
 
 
 # every kernel name a timing_kernels() call has reported in this process (the kernel-coverage check of the GPU suite

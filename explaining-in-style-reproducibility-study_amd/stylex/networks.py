@@ -387,7 +387,9 @@ class Generator(nn.Module):  # reference :747-825
             return ops.initial_block(styles, self.to_initial_block.weight)
         return self.initial_block.expand(styles.shape[0], -1, -1, -1)
 
-    def forward(self, styles, input_noise, get_style_coords=False):
+    def forward(self, styles, input_noise, get_style_coords=False, block_inputs=None):
+        """`block_inputs`: a list that receives (feature map, RGB) as they ENTER every block (the block's attention applied) —
+        what attfind.counterfactual_images restarts the generator from."""
         x = self.initial_conv(self.first_activation(styles))
         rgb, coords = None, []
         # The toRGB chain runs on the caller's stream.  (Rounds 1-5 kept an opt-in variant that ran it one block behind on a
@@ -399,6 +401,8 @@ class Generator(nn.Module):  # reference :747-825
         for li, block in enumerate(self.blocks):
             if exists(self.attns[li]):
                 x = self.attns[li](x)
+            if block_inputs is not None:
+                block_inputs.append((x, rgb))
             x, sc = block.forward_main(x, per_layer[li], input_noise)
             coords.append(sc)
             rgb = block.to_rgb(x, rgb, per_layer[li], style=block.__dict__.pop("_rgb_style", None), padded=True)

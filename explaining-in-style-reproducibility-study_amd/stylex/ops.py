@@ -1240,6 +1240,12 @@ class HipOps:
                                  down is not None)
 
     @staticmethod
+    def style_edit_levels(coords, smin, smax, sindex, direction, base_class, level_k, seg_start, shift_size):
+        """The edited style vectors of attfind.counterfactual_images for all levels of an image batch, one launch; the
+        blocks' style segments as dense [L, N, w] tensors."""
+        return hb.style_edit_levels(coords, smin, smax, sindex, direction, base_class, level_k, seg_start, shift_size)
+
+    @staticmethod
     def rowwise_sumsq(x2d):
         return _RowSumSq.apply(x2d)
 

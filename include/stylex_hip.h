@@ -674,6 +674,24 @@ int stylex_initial_block_bwd_data(const void* gx, const void* w, float* dstyles,
 int stylex_initial_block_bwd_weight(const float* styles, const void* gx, float* dw, const int64_t* shape, int act_dtype,
                                     void* stream);
 
+/* ---- counterfactual style edits (csrc/style_edit.hip; attfind.counterfactual_images) -------------------------
+ * The edited style vectors of N images for L levels in one launch (reference stylex/FID_TensorFlow.ipynb cell 20).
+ * coords [N][S] fp32; smin, smax [S] fp32; sindex, direction [K]; base_class [N]; level_k [L]; seg_start [G + 1], all int32.
+ * Level l applies the first level_k[l] list entries IN LIST ORDER to every image (0: a copy):
+ *   if sindex[j] == c:  t = ((direction[j] == 0) != (base_class[n] == 0)) ? smin[c] : smax[c];  v = v + (t - v) * shift_size
+ * with three separately rounded fp32 operations (no fma).  A coordinate listed twice moves from its already moved value.
+ * out, L * N * S floats, segment-major: column c of segment g (seg_start[g] <= c < seg_start[g + 1], width w) at
+ *   L * N * seg_start[g] + (l * N + n) * w + (c - seg_start[g]).  Every element is written once; nothing else is touched.
+ * The caller guarantees what the device cannot report: 0 <= sindex < S, direction in {0, 1}, 0 <= level_k <= K,
+ * seg_start[0] = 0 < ... < seg_start[G] = S (an entry that breaks this is skipped or clamped, never an access outside).
+ * STYLEX_EINVAL, before the device is touched: a null pointer, a size below 1, K > stylex_style_edit_max_k(), G > S,
+ * L * N above 2^31 - 1. */
+int64_t stylex_style_edit_max_k(void);
+int stylex_style_edit_levels(const float* coords, const float* smin, const float* smax, const int32_t* sindex,
+                             const int32_t* direction, const int32_t* base_class, const int32_t* level_k,
+                             const int32_t* seg_start, float* out, int64_t N, int64_t S, int64_t K, int64_t L, int64_t G,
+                             float shift_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
