@@ -600,75 +600,148 @@ def _natural_noise(inoise):
     return nat
 
 
+# The fused modulated conv (Conv2DMod + noise + LeakyReLU), the generator's hot node.  As for the fused DiscriminatorBlock
+# below, how it runs is decided ONCE, by _modconv_plan in the forward; the backward reads the plan and the named saved
+# state, never the environment or the library, and a pass outside autograd can drive the two stage functions directly.
+_ModConvPlan = collections.namedtuple(
+    "_ModConvPlan", "prec pad lrelu pre nat fwd_noise prep prep_ok bwd_noise fold dgrad scale_reduce")
+_ModConvSaved = collections.namedtuple("_ModConvSaved", "x s1 d w noise nw nb y noise_nat")
+
+
+def _modconv_plan(x_shape, w_shape, x_cuda, has_d, has_style, has_noise, has_nat, nat_side, pad, lrelu, prec,
+                  has_symbol=hb.has_symbol):
+    """Every decision of one fused modulated conv, from shapes, what is present, the precision mode and the two environment
+    switches (read per call: tests toggle them).  has_nat: the noise plane is at hand in natural order (_natural_noise) —
+    or, asked by the call site before it transposes, can be; nat_side: its side length.  The library probe is an argument
+    so that the rules can be evaluated without the kernel library."""
+    def on(name):
+        return os.environ.get(name, "1") != "0"
+
+    cin, cout, bf16 = x_shape[1], w_shape[0], prec == hb.BF16_ACT
+    # <= 8x8 px layers: the modulation is applied to the (tiny) input tensor up front, so that the launch can take the
+    # LDS-DMA implicit-GEMM kernel (conv_gather.hip: a DMA cannot scale in flight); same rounding as the in-kernel
+    # staging (product rounded to bf16 once)
+    pre = bf16 and has_style and x_shape[2] * x_shape[3] <= 64 and cin % 64 == 0
+    # the natural-order plane serves device inputs (STYLEX_NOISE_NAT=0: every read is the transposed one)
+    nat = bool(has_nat and x_cuda and on("STYLEX_NOISE_NAT"))
+    # The two reads are decided separately and may differ: the forward epilogue loads 4 pixels of a row at once, so it
+    # takes the natural plane only at a side that is a multiple of 4; the prep pass reads rows of it at any side, if the
+    # library has the entry point (one from before it — STYLEX_HIP_LIB=<older build>, A/B runs — keeps the transposed
+    # plane).  Side 9: transposed forward, natural backward.
+    fwd_noise = "none" if not has_noise else "natural" if nat and nat_side % 4 == 0 else "transposed"
+    bwd_noise = "natural" if nat and has_symbol("stylex_modconv_bwd_prep_nat") else "transposed"
+    # modconv_bwd_prep (LeakyReLU mask, noise / bias sums, the demodulation gradient's sum) runs over the saved y; where
+    # the channel count rules it out, the BACKWARD raises: a forward under no_grad works at any count
+    prep, prep_ok = bool(lrelu or has_d or has_noise), _reducible(cout)
+    # the gradient leaves the prep pass pre-multiplied by d: a scale-free operand for the data gradient, eligible for the
+    # LDS-DMA kernels (halo / small-spatial gather), and no dy scale in the weight gradient
+    fold = prep and prep_ok and has_d and prec != hb.F32 and on("STYLEX_FOLD_D")
+    # else, small layer: d applied to the (tiny) gradient tensor up front; else the data gradient's in_scale (d or None)
+    dgrad = "folded" if fold else "prescaled" if pre and has_d else "in_scale"
+    return _ModConvPlan(prec, pad, bool(lrelu), pre, nat, fwd_noise, prep, prep_ok, bwd_noise, fold, dgrad,
+                        _reducible(cin))
+
+
+def _modconv_forward(plan, x, s1, d, w, noise, nw, nb, noise_nat):
+    """(y, saved): y = lrelu?( d[b,o] * conv(x * s1[b,i], w) + noise[b,w,h]*nw[o] + nb[o] )"""
+    x = _cl(x)
+    if plan.pre:
+        x_in, s_in = (x.float() * s1[:, :, None, None]).to(x.dtype).contiguous(memory_format=torch.channels_last), None
+    else:
+        x_in, s_in = x, s1
+    read = dict(noise=noise_nat, noise_natural=True) if plan.fwd_noise == "natural" else dict(noise=noise)
+    y = hb.conv2d_fwd(x_in, w, 1, plan.pad, plan.prec, in_scale=s_in, out_scale=d, noise_w=nw, noise_b=nb,
+                      lrelu=plan.lrelu, **read)
+    # x: the unmodulated input, also with plan.pre (the backward's reductions are over it)
+    return y, _ModConvSaved(x, s1, d, w, noise, nw, nb, y if plan.prep else None, noise_nat if plan.nat else None)
+
+
+def _modconv_backward(plan, saved, gy, need):
+    """(gx, gs1, gd, gw, gnw, gnb); need = (x, s1, w): which of those three gradients are wanted (gd, gnw and gnb come
+    out of the prep pass either way)."""
+    x, s1, d, w, noise, nw, nb, y, noise_nat = saved
+    want_x, want_s1, want_w = need
+    prec = plan.prec
+    gz = _cl(gy)
+    gd = gnw = gnb = None
+    if plan.prep:
+        if not plan.prep_ok:
+            raise hb.StylexHipError("fused modulated conv needs C_out % 4 == 0")
+        natural = plan.bwd_noise == "natural"
+        gz, sums = hb.modconv_bwd_prep(gz, y, noise_nat if natural else noise, nw, nb, plan.lrelu,
+                                       gz_scale=d if plan.fold else None, noise_natural=natural)
+        if d is not None:
+            gd = sums[:, 0] / d
+        if noise is not None:
+            gnw, gnb = sums[:, 1:3].sum(0)  # one reduction launch for both (the same per-element sums)
+    gx = gs1 = gw = None
+    if want_x or want_s1:
+        if plan.dgrad == "prescaled":
+            gzd = (gz.float() * d[:, :, None, None]).to(gz.dtype).contiguous(memory_format=torch.channels_last)
+            t = hb.conv2d_bwd_data(gzd, w, tuple(x.shape), 1, plan.pad, prec)
+        else:
+            t = hb.conv2d_bwd_data(gz, w, tuple(x.shape), 1, plan.pad, prec, in_scale=None if plan.fold else d)
+        if plan.scale_reduce:
+            gx, gs1 = hb.scale_reduce(x, t, s1, want_gx=want_x)
+        else:
+            gs1 = (x.float() * t.float()).sum(dim=(2, 3))
+            gx = (t.float() * s1[:, :, None, None]).to(t.dtype)
+    if want_w:
+        gw = hb.conv2d_bwd_weight(x, gz, tuple(w.shape), 1, plan.pad, prec, x_scale=s1, dy_scale=None if plan.fold else d)
+    return gx, gs1, gd, gw, gnw, gnb
+
+
 class _ModConvFast(torch.autograd.Function):
-    """y = lrelu?( d[b,o] * conv(x * s1[b,i], w) + noise[b,w,h]*nw[o] + nb[o] )   (Conv2DMod + noise + act)"""
+    """y = lrelu?( d[b,o] * conv(x * s1[b,i], w) + noise[b,w,h]*nw[o] + nb[o] )   (Conv2DMod + noise + act).  The work
+    is in _modconv_forward / _modconv_backward; this class only builds the plan and saves and restores their state."""
 
     @staticmethod
     def forward(ctx, x, s1, d, w, noise, nw, nb, pad, lrelu, noise_nat=None):
-        x = _cl(x)
-        # <= 8x8 px layers: the modulation is applied to the (tiny) input tensor up front, so that the launch can take
-        # the LDS-DMA implicit-GEMM kernel (conv_gather.hip: a DMA cannot scale in flight); same rounding as the
-        # in-kernel staging (product rounded to bf16 once)
-        pre = _PRECISION == hb.BF16_ACT and s1 is not None and x.shape[2] * x.shape[3] <= 64 and x.shape[1] % 64 == 0
-        ctx.pre = pre
-        if pre:
-            x_in, s_in = (x.float() * s1[:, :, None, None]).to(x.dtype).contiguous(memory_format=torch.channels_last), None
-        else:
-            x_in, s_in = x, s1
-        if noise_nat is not None and noise_nat.shape[1] % 4 == 0:
-            y = hb.conv2d_fwd(x_in, w, 1, pad, _PRECISION, in_scale=s_in, out_scale=d, noise=noise_nat, noise_w=nw,
-                              noise_b=nb, lrelu=lrelu, noise_natural=True)
-        else:
-            y = hb.conv2d_fwd(x_in, w, 1, pad, _PRECISION, in_scale=s_in, out_scale=d, noise=noise, noise_w=nw, noise_b=nb,
-                              lrelu=lrelu)
-        ctx.save_for_backward(x, s1, d, w, noise, nw, nb, y if (lrelu or d is not None or noise is not None) else None,
-                              noise_nat)
-        ctx.cfg = (pad, lrelu)
+        ctx.plan = _modconv_plan(tuple(x.shape), tuple(w.shape), x.is_cuda, d is not None, s1 is not None,
+                                 noise is not None, noise_nat is not None,
+                                 noise_nat.shape[1] if noise_nat is not None else 0, pad, lrelu, _PRECISION)
+        y, saved = _modconv_forward(ctx.plan, x, s1, d, w, noise, nw, nb, noise_nat)
+        ctx.save_for_backward(*saved)
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        x, s1, d, w, noise, nw, nb, y, noise_nat = ctx.saved_tensors
-        pad, lrelu = ctx.cfg
-        gy = _cl(gy)
-        gd = gnw = gnb = None
-        folded = False  # gz already carries the demodulation coefficient d
-        if y is not None and _reducible(gy.shape[1]):
-            fold = d is not None and _PRECISION != hb.F32 and os.environ.get("STYLEX_FOLD_D", "1") != "0"
-            # the plane the forward read: rows of the plane instead of a strided gather (a library from before the entry
-            # point — STYLEX_HIP_LIB=<older build>, A/B runs — keeps the transposed plane)
-            if noise_nat is not None and hb.has_symbol("stylex_modconv_bwd_prep_nat"):
-                gz, sums = hb.modconv_bwd_prep(gy, y, noise_nat, nw, nb, lrelu, gz_scale=d if fold else None,
-                                               noise_natural=True)
-            else:
-                gz, sums = hb.modconv_bwd_prep(gy, y, noise, nw, nb, lrelu, gz_scale=d if fold else None)
-            folded = fold
-            if d is not None:
-                gd = sums[:, 0] / d
-            if noise is not None:
-                gnw, gnb = sums[:, 1:3].sum(0)  # one reduction launch for both (the same per-element sums)
-        elif y is not None:
-            raise hb.StylexHipError("fused modulated conv needs C_out % 4 == 0")
-        else:
-            gz = gy
-        gx = gs1 = gw = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            if folded:  # scale-free operand: eligible for the LDS-DMA kernels (halo / small-spatial gather)
-                t = hb.conv2d_bwd_data(gz, w, tuple(x.shape), 1, pad, _PRECISION)
-            elif ctx.pre and d is not None:  # small layer: demodulation applied to the (tiny) gradient tensor up front
-                gzd = (gz.float() * d[:, :, None, None]).to(gz.dtype).contiguous(memory_format=torch.channels_last)
-                t = hb.conv2d_bwd_data(gzd, w, tuple(x.shape), 1, pad, _PRECISION)
-            else:
-                t = hb.conv2d_bwd_data(gz, w, tuple(x.shape), 1, pad, _PRECISION, in_scale=d)
-            if _reducible(x.shape[1]):
-                gx, gs1 = hb.scale_reduce(x, t, s1, want_gx=ctx.needs_input_grad[0])
-            else:
-                gs1 = (x.float() * t.float()).sum(dim=(2, 3))
-                gx = (t.float() * s1[:, :, None, None]).to(t.dtype)
-        if ctx.needs_input_grad[3]:
-            gw = hb.conv2d_bwd_weight(x, gz, tuple(w.shape), 1, pad, _PRECISION, x_scale=s1, dy_scale=None if folded else d)
+        need = ctx.needs_input_grad
+        gx, gs1, gd, gw, gnw, gnb = _modconv_backward(ctx.plan, _ModConvSaved(*ctx.saved_tensors), gy,
+                                                      (need[0], need[1], need[3]))
         return gx, gs1, gd, gw, None, gnw, gnb, None, None, None
+
+
+def _modconv_fused(x, s1, d, weight, inoise=None, nw=None, nb=None):
+    """One Conv2DMod — with `inoise` plus its noise and LeakyReLU — on the fused node, or None when the composable path
+    must run: a double backward may be requested, or the output channels are no multiple of 4.  The 3 outputs of a to-RGB
+    conv run as 4 (a zero filter, d = 1) and are sliced back; a noise layer with 3 outputs takes the composition."""
+    n_out = weight.shape[0]
+    pad_out = n_out == 3 and inoise is None
+    if not fast_enabled() or (n_out + pad_out) % 4 != 0:
+        return None
+    if pad_out:
+        weight = torch.cat([weight, weight.new_zeros(1, *weight.shape[1:])], dim=0)
+        if d is not None:
+            d = torch.cat([d, d.new_ones(d.shape[0], 1)], dim=1)
+    pad = (weight.shape[2] - 1) // 2  # _get_same_padding for stride 1, dilation 1 (:644-645)
+    if inoise is None:
+        y = _ModConvFast.apply(x, s1, d, weight, None, None, None, pad, False)
+        return y[:, :3] if pad_out else y
+    # asked before the transpose (once per generator forward): would this conv read the natural-order plane?
+    want_nat = _modconv_plan(tuple(x.shape), tuple(weight.shape), x.is_cuda, has_d=d is not None, has_style=True,
+                             has_noise=True, has_nat=True, nat_side=inoise.shape[1], pad=pad, lrelu=True,
+                             prec=_PRECISION).nat
+    return _ModConvFast.apply(x, s1, d, weight, inoise[:, :, :, 0], nw, nb, pad, True,
+                              _natural_noise(inoise) if want_nat else None)
+
+
+def _torgb_route(x, weight, demod):
+    """Does this modulated conv over the (activation-dtype) x run as the streaming to-RGB kernel (_ToRGBFast)?  The 1x1,
+    3-output, non-demodulated conv of RGBBlock, first order only, where hb.torgb_ok takes the input."""
+    return (fast_enabled() and weight.shape[0] == 3 and tuple(weight.shape[2:]) == (1, 1) and not demod
+            and hb.torgb_ok(x))
 
 
 class _ToRGBFast(torch.autograd.Function):
@@ -766,7 +839,8 @@ class _DownS2DFast(torch.autograd.Function):
 
 
 # The fused DiscriminatorBlock.  How a block runs is decided ONCE, by _dblock_plan in the forward; the backward and the
-# gradient-penalty tangent pass (gp_tangent.py) read the plan and the named saved state, never the environment.
+# gradient-penalty tangent pass (gp_tangent.py) read the plan and the named saved state, never the environment.  The fused
+# modulated conv above (_modconv_plan, _ModConvSaved, _modconv_forward / _modconv_backward) keeps the same promise.
 _DBlockPlan = collections.namedtuple(
     "_DBlockPlan", "prec downsample cin pad extra res_gemm s2d fold_res mask1 mask2 alg wgrad_bias c")
 _DBlockSaved = collections.namedtuple("_DBlockSaved", "x xs y1 y2 xb m1 m2 w_res w1 w2 w3")
@@ -1142,21 +1216,14 @@ class HipOps:
         `coeffs` = mod_coeffs(style, weight, demod, eps) when the caller computed them ahead (side stream)."""
         x = _act(x)
         s1, d_pre = coeffs if coeffs is not None else mod_coeffs(style, weight, demod, eps)
-        k = weight.shape[2]
-        pad = (k - 1) // 2  # _get_same_padding for stride 1, dilation 1 (:644-645)
-        n_out = weight.shape[0]
-        if fast_enabled() and n_out == 3 and k == 1 and not demod and hb.torgb_ok(x):
+        if _torgb_route(x, weight, demod):
             return _ToRGBFast.apply(x, s1, weight)[:, :3]  # to-RGB: a 3-column GEMM is an HBM stream, not MFMA work
-        w_run = weight
-        if n_out == 3:
-            w_run = torch.cat([weight, weight.new_zeros(1, *weight.shape[1:])], dim=0)
-        if fast_enabled() and w_run.shape[0] % 4 == 0:
-            d = d_pre
-            if demod and n_out == 3:
-                d = torch.cat([d, d.new_ones(d.shape[0], 1)], dim=1)
-            y = _ModConvFast.apply(x, s1, d, w_run, None, None, None, pad, False)
-            return y[:, :3] if n_out == 3 else y
-        y = _Conv.apply(x * s1[:, :, None, None], w_run, 1, pad)
+        y = _modconv_fused(x, s1, d_pre, weight)
+        if y is not None:
+            return y
+        n_out = weight.shape[0]
+        w_run = torch.cat([weight, weight.new_zeros(1, *weight.shape[1:])], dim=0) if n_out == 3 else weight
+        y = _Conv.apply(x * s1[:, :, None, None], w_run, 1, (weight.shape[2] - 1) // 2)
         if n_out == 3:
             y = y[:, :3]
         if demod:
@@ -1168,11 +1235,10 @@ class HipOps:
         """lrelu(Conv2DMod(x, style) + noise) of GeneratorBlock (:696-714) as one fused kernel when no
         double backward can be requested, else the differentiable composition."""
         x = _act(x)
-        if fast_enabled() and weight.shape[0] % 4 == 0:
-            s1, d = coeffs if coeffs is not None else mod_coeffs(style, weight, demod, eps)
-            plane = inoise[:, :, :, 0]
-            nat = _natural_noise(inoise) if (x.is_cuda and os.environ.get("STYLEX_NOISE_NAT", "1") != "0") else None
-            return _ModConvFast.apply(x, s1, d, weight, plane, noise_w, noise_b, (weight.shape[2] - 1) // 2, True, nat)
+        coeffs = coeffs if coeffs is not None else mod_coeffs(style, weight, demod, eps)
+        y = _modconv_fused(x, *coeffs, weight, inoise, noise_w, noise_b)
+        if y is not None:
+            return y
         return HipOps.noise_act(HipOps.modulated_conv2d(x, style, weight, demod, eps, coeffs=coeffs), inoise, noise_w,
                                 noise_b)
 
@@ -1214,7 +1280,7 @@ class HipOps:
         if not fast_enabled() or os.environ.get("STYLEX_RGB_TAIL", "1") == "0":
             return None
         x = _act(x)
-        if tuple(weight.shape[2:]) != (1, 1) or weight.shape[0] != 3 or not hb.torgb_ok(x):
+        if not _torgb_route(x, weight, demod=False):
             return None
         if prev_rgb is not None and (prev_rgb.shape[1] != 4 or prev_rgb.dtype != x.dtype):
             return None

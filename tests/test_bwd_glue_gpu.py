@@ -479,6 +479,38 @@ def test_modconv_noise_act_fast_path_vs_float64(case, prec, fold, rec, monkeypat
         rec.ratio(close_ratio(got, want.grad, tol), "grad " + name)
 
 
+def test_modconv_backward_follows_the_forward_plan_not_the_environment(monkeypatch):
+    """STYLEX_FOLD_D is read once, when the forward builds the plan: flipping it before .backward() changes no bit of the
+    five gradients, whichever way round (2x64x40x8x8, side 8, bf16: the `pre` layer, "folded" against "prescaled")."""
+    B, Ci, Co, H, W, ns = 2, 64, 40, 8, 8, 8
+    g = torch.Generator().manual_seed(5)
+    x = rounded(torch.randn(B, Ci, H, W, generator=g), "bf16")
+    style = torch.randn(B, Ci, generator=g) * 0.5
+    w = torch.randn(Co, Ci, 3, 3, generator=g) / (Ci * 9) ** 0.5
+    nw, nb = torch.randn(Co, generator=g), torch.randn(Co, generator=g)
+    inoise = torch.rand(B, ns, ns, 1, generator=g).to(DEV)
+    r = dev_cl(rounded(torch.randn(B, Co, H, W, generator=g), "bf16"))
+
+    def grads(fold_fwd, fold_bwd):
+        monkeypatch.setenv("STYLEX_FOLD_D", fold_fwd)
+        leaves = [dev_cl(x).requires_grad_()] + [t.to(DEV).requires_grad_() for t in (style, w, nw, nb)]
+        y = ops.modconv_noise_act(leaves[0], leaves[1], leaves[2], inoise, leaves[3], leaves[4])
+        assert "ModConvFast" in type(y.grad_fn).__name__
+        assert y.grad_fn.plan.dgrad == ("folded" if fold_fwd == "1" else "prescaled")
+        monkeypatch.setenv("STYLEX_FOLD_D", fold_bwd)
+        (y.float() * r).sum().backward()
+        return [t.grad for t in leaves]
+
+    ops.set_precision("bf16")
+    prev = ops.set_fast(True)
+    try:
+        for fwd, bwd in (("0", "1"), ("1", "0")):
+            for name, got, want in zip(("x", "style", "weight", "noise_w", "noise_b"), grads(fwd, bwd), grads(fwd, fwd)):
+                assert got is not None and torch.equal(got, want), (fwd, bwd, name)
+    finally:
+        ops.set_fast(prev)
+
+
 @pytest.mark.against_definition
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
 @pytest.mark.parametrize("case", [(3, 12, 12, 9, 9), (5, 64, 64, 24, 40)], ids=["3x12x12x9x9", "5x64x64x24x40"])
