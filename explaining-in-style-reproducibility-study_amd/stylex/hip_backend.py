@@ -740,6 +740,20 @@ def pack_weight_s2d(w, scale=None):
     return packs.get((w,), "s2d", build, _packable(w), scale=scale, recipe=lambda p: pack_weight_s2d(p, scale))
 
 
+def conv2d_fwd_s2d(x2, w, precision, **epi):
+    """conv2d_fwd of the 3x3 / stride-2 conv with the OIHW {N,C,3,3} parameter w, its (blurred) input given space-to-depth
+    (x2: [B, 4C, H/2, W/2]): a 3x3 / stride-1 conv over 4C channels, structurally-zero taps skipped."""
+    n, c = int(w.shape[0]), int(w.shape[1])
+    return conv2d_fwd(x2, None, 1, 1, precision, packed=pack_weight_s2d(w)[0], w_shape=(n, 4 * c, 3, 3), s2d_c=c, **epi)
+
+
+def conv2d_bwd_data_s2d(gy, w, x2_shape, precision, scale=None, **epi):
+    """Data gradient of conv2d_fwd_s2d, space-to-depth like x2; scale: a constant folded into the packed operand."""
+    n, c = int(w.shape[0]), int(w.shape[1])
+    return conv2d_bwd_data(gy, None, x2_shape, 1, 1, precision, packed=pack_weight_s2d(w, scale)[1],
+                           w_shape=(n, 4 * c, 3, 3), s2d_c=c, **epi)
+
+
 _S2D_WGRAD_OK = {}
 
 

@@ -23,7 +23,6 @@ double with ``use_impl`` to exercise the host logic without a GPU.
 """
 import collections
 import math
-
 import os
 
 import torch
@@ -94,103 +93,102 @@ def _want_param_grad(ctx, i):
     return ctx.needs_input_grad[i] and not _INPUTS_ONLY
 
 
-def _gemm_1x1(t, w, stride, pad, s2d):
+# How the launches of one plain conv run: stride, pad, s2d (C of the original stride-2 conv when the input is its
+# space-to-depth image, else 0) and gemm (the static half of _gemm_1x1).  Made by _conv_plan; the triad and _ConvBiasActDD keep
+# it in ctx and hand it to the nodes their backward creates, so a double backward takes the route its forward chose.
+_ConvLaunch = collections.namedtuple("_ConvLaunch", "stride pad s2d gemm")
+
+
+def _gemm_1x1(t, launch):
     """A 1x1 / stride-1 conv in the bf16 mode is a plain GEMM: forward and data gradient of the composable
     (double-differentiable) triad go to hipBLASLt like the fused DiscriminatorBlock's residual conv (17-130 TF/s on the
     generic kernel, 3.2 ms per gradient-penalty step).  The WEIGHT gradient stays on the deterministic split-K kernel:
     letting ATen differentiate an addmm instead made two identically seeded Trainers diverge (its K = B*H*W weight-
-    gradient GEMM takes a split-K algorithm with atomic accumulation; tools/determinism_check.py 4 of 4 runs)."""
-    return (not s2d and stride == 1 and pad == 0 and _PRECISION == hb.BF16_ACT and t.is_cuda and t.dtype == torch.bfloat16
-            and w.dim() == 4 and tuple(w.shape[2:]) == (1, 1) and os.environ.get("STYLEX_RES_GEMM", "1") != "0"
-            and os.environ.get("STYLEX_RES_GEMM_DD", "1") != "0")
+    gradient GEMM takes a split-K algorithm with atomic accumulation; tools/determinism_check.py 4 of 4 runs).
+    launch.gemm: what shapes, mode and switches say (_conv_plan); what the tensor says is asked here."""
+    return launch.gemm and t.is_cuda and t.dtype == torch.bfloat16
 
 
-def _fwd(x, w, stride, pad, s2d, **epi):
-    """conv forward; s2d = C of the original stride-2 conv when x is its space-to-depth image."""
-    if _gemm_1x1(x, w, stride, pad, s2d) and not any(v is not None and v is not False for k, v in epi.items()
-                                                      if k not in ("bias", "res_scale")):
+def _fwd(x, w, launch, **epi):
+    """conv forward; the GEMM has no epilogue other than the bias."""
+    if _gemm_1x1(x, launch) and not any(v is not None and v is not False for k, v in epi.items()
+                                        if k not in ("bias", "res_scale")):
         return hb.conv1x1_gemm_fwd(_cl(x), w, epi.get("bias"))
-    if s2d:
-        wf2, _ = hb.pack_weight_s2d(w)
-        return hb.conv2d_fwd(x, None, 1, 1, _PRECISION, packed=wf2, w_shape=(w.shape[0], 4 * s2d, 3, 3), s2d_c=s2d, **epi)
-    return hb.conv2d_fwd(x, w, stride, pad, _PRECISION, **epi)
+    if launch.s2d:
+        return hb.conv2d_fwd_s2d(x, w, _PRECISION, **epi)
+    return hb.conv2d_fwd(x, w, launch.stride, launch.pad, _PRECISION, **epi)
 
 
-def _bwd_data(gy, w, x_shape, stride, pad, s2d):
-    if _gemm_1x1(gy, w, stride, pad, s2d):
+def _bwd_data(gy, w, x_shape, launch):
+    if _gemm_1x1(gy, launch):
         return hb.conv1x1_gemm_bwd_data(_cl(gy), w)
-    if s2d:
-        _, wb2 = hb.pack_weight_s2d(w)
-        return hb.conv2d_bwd_data(gy, None, x_shape, 1, 1, _PRECISION, packed=wb2, w_shape=(w.shape[0], 4 * s2d, 3, 3),
-                                  s2d_c=s2d)
-    return hb.conv2d_bwd_data(gy, w, x_shape, stride, pad, _PRECISION)
+    if launch.s2d:
+        return hb.conv2d_bwd_data_s2d(gy, w, x_shape, _PRECISION)
+    return hb.conv2d_bwd_data(gy, w, x_shape, launch.stride, launch.pad, _PRECISION)
 
 
-def _bwd_weight(x, gy, w_shape, stride, pad, s2d):
-    if s2d:
+def _bwd_weight(x, gy, w_shape, launch):
+    if launch.s2d:
         return hb.conv2d_bwd_weight_s2d(x, gy, tuple(w_shape), _PRECISION)
-    return hb.conv2d_bwd_weight(x, gy, w_shape, stride, pad, _PRECISION)
+    return hb.conv2d_bwd_weight(x, gy, w_shape, launch.stride, launch.pad, _PRECISION)
 
 
 class _Conv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, stride, pad, s2d=0):
+    def forward(ctx, x, w, launch):
         x = _cl(x)
         ctx.save_for_backward(x, w)
-        ctx.cfg = (stride, pad, s2d)
-        return _fwd(x, w, stride, pad, s2d)
+        ctx.launch = launch
+        return _fwd(x, w, launch)
 
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        stride, pad, s2d = ctx.cfg
         gx = gw = None
         if ctx.needs_input_grad[0]:
-            gx = _Dgrad.apply(gy, w, tuple(x.shape), stride, pad, s2d)
+            gx = _Dgrad.apply(gy, w, tuple(x.shape), ctx.launch)
         if _want_param_grad(ctx, 1):
-            gw = _Wgrad.apply(x, gy, tuple(w.shape), stride, pad, s2d)
-        return gx, gw, None, None, None
+            gw = _Wgrad.apply(x, gy, tuple(w.shape), ctx.launch)
+        return gx, gw, None
 
 
 class _Dgrad(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, gy, w, x_shape, stride, pad, s2d=0):
+    def forward(ctx, gy, w, x_shape, launch):
         gy = _cl(gy)
         ctx.save_for_backward(gy, w)
-        ctx.cfg = (x_shape, stride, pad, s2d)
-        return _bwd_data(gy, w, x_shape, stride, pad, s2d)
+        ctx.launch = launch
+        return _bwd_data(gy, w, x_shape, launch)
 
     @staticmethod
     def backward(ctx, ggx):
         gy, w = ctx.saved_tensors
-        x_shape, stride, pad, s2d = ctx.cfg
         d_gy = d_w = None
         if ctx.needs_input_grad[0]:
-            d_gy = _Conv.apply(ggx, w, stride, pad, s2d)
+            d_gy = _Conv.apply(ggx, w, ctx.launch)
         if _want_param_grad(ctx, 1):
-            d_w = _Wgrad.apply(ggx, gy, tuple(w.shape), stride, pad, s2d)
-        return d_gy, d_w, None, None, None, None
+            d_w = _Wgrad.apply(ggx, gy, tuple(w.shape), ctx.launch)
+        return d_gy, d_w, None, None
 
 
 class _Wgrad(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gy, w_shape, stride, pad, s2d=0):
+    def forward(ctx, x, gy, w_shape, launch):
         x, gy = _cl(x), _cl(gy)
         ctx.save_for_backward(x, gy)
-        ctx.cfg = (w_shape, stride, pad, s2d)
-        return _bwd_weight(x, gy, w_shape, stride, pad, s2d)
+        ctx.launch = launch
+        return _bwd_weight(x, gy, w_shape, launch)
 
     @staticmethod
     def backward(ctx, ggw):
         x, gy = ctx.saved_tensors
-        w_shape, stride, pad, s2d = ctx.cfg
         d_x = d_gy = None
         ggw = ggw.contiguous()
         if ctx.needs_input_grad[0]:
-            d_x = _Dgrad.apply(gy, ggw, tuple(x.shape), stride, pad, s2d)
+            d_x = _Dgrad.apply(gy, ggw, tuple(x.shape), ctx.launch)
         if ctx.needs_input_grad[1]:
-            d_gy = _Conv.apply(x, ggw, stride, pad, s2d)
-        return d_x, d_gy, None, None, None, None
+            d_gy = _Conv.apply(x, ggw, ctx.launch)
+        return d_x, d_gy, None, None
 
 
 # ------------------------------------------------------------------------------------------
@@ -512,69 +510,73 @@ def _grad_prologue(gy, y, lrelu, scale, want_gb):
     return gz, (gz.sum(dim=(0, 2, 3), dtype=torch.float32) if want_gb else None)
 
 
+# The fused plain conv: conv + bias + residual merge + activation in one forward launch.  How it runs is decided ONCE, by
+# _conv_plan in the calling op (HipOps.conv2d / .blur_down), and reaches the Functions as the plan's launch record.
+_ConvEpi = collections.namedtuple("_ConvEpi", "launch lrelu scale has_bias has_res untimed")
+_ConvSaved = collections.namedtuple("_ConvSaved", "x w y")
+
+
+def _conv_forward(launch, x, w, bias, residual, lrelu, res_scale):
+    """(y, epi, saved): y = lrelu?( (conv(x, w) + bias + residual) * res_scale ).  With launch.s2d, x is the space-to-depth
+    image of a stride-2 conv's input: a 3x3/s1 conv over 4C channels on the LDS-halo kernels, structurally-zero taps skipped
+    (exactly the original 9*C work)."""
+    x = _cl(x)
+    if residual is not None:
+        residual = _cl(residual)
+    y = _fwd(x, w, launch, bias=bias, lrelu=lrelu, residual=residual, res_scale=res_scale)
+    # untimed: built inside hb.timing_pause() (a frozen network's layer): so is its fused backward
+    epi = _ConvEpi(launch, lrelu, float(res_scale) if residual is not None else 1.0, bias is not None,
+                   residual is not None, hb.timing_paused())
+    return y, epi, _ConvSaved(x, w, y if lrelu else None)
+
+
+def _conv_backward(epi, saved, gy, need):
+    """(gx, gw, gb, gres), first order only; need = the node's needs_input_grad."""
+    x, w, y = saved
+    # (no bias gradient in the generator phase, D frozen: no reduction launch)
+    gz, gb = _grad_prologue(_cl(gy), y, epi.lrelu, epi.scale, epi.has_bias and need[2])
+    with (hb.timing_pause() if epi.untimed else _nullcontext()):
+        gx = _bwd_data(gz, w, tuple(x.shape), epi.launch) if need[0] else None
+        gw = _bwd_weight(x, gz, tuple(w.shape), epi.launch) if need[1] else None
+    return gx, gw, gb, (gz if epi.has_res and need[3] else None)
+
+
 class _ConvBiasActFast(torch.autograd.Function):
-    """y = lrelu?( (conv(x, w) + bias + residual) * res_scale )"""
+    """_conv_forward / _conv_backward as a once-differentiable node; the class only saves and restores their state."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, residual, stride, pad, lrelu, res_scale):
-        x = _cl(x)
-        if residual is not None:
-            residual = _cl(residual)
-        y = hb.conv2d_fwd(x, w, stride, pad, _PRECISION, bias=bias, lrelu=lrelu, residual=residual,
-                          res_scale=res_scale)
-        ctx.save_for_backward(x, w, y if lrelu else None)
-        ctx.cfg = (stride, pad, lrelu, float(res_scale) if residual is not None else 1.0, bias is not None,
-                   residual is not None)
-        ctx.untimed = hb.timing_paused()  # built inside hb.timing_pause() (a frozen network's layer): so is its backward
+    def forward(ctx, x, w, bias, residual, launch, lrelu, res_scale):
+        y, ctx.epi, saved = _conv_forward(launch, x, w, bias, residual, lrelu, res_scale)
+        ctx.save_for_backward(*saved)
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        x, w, y = ctx.saved_tensors
-        stride, pad, lrelu, scale, has_bias, has_res = ctx.cfg
-        # (no bias gradient in the generator phase, D frozen: no reduction launch)
-        gz, gb = _grad_prologue(_cl(gy), y, lrelu, scale, has_bias and ctx.needs_input_grad[2])
-        with (hb.timing_pause() if ctx.untimed else _nullcontext()):
-            gx = hb.conv2d_bwd_data(gz, w, tuple(x.shape), stride, pad, _PRECISION) if ctx.needs_input_grad[0] else None
-            gw = hb.conv2d_bwd_weight(x, gz, tuple(w.shape), stride, pad, _PRECISION) if ctx.needs_input_grad[1] else None
-        return gx, gw, gb, (gz if has_res and ctx.needs_input_grad[3] else None), None, None, None, None
+        return _conv_backward(ctx.epi, _ConvSaved(*ctx.saved_tensors), gy, ctx.needs_input_grad) + (None, None, None)
 
 
-class _ConvBiasActDD(torch.autograd.Function):
-    """Same fused forward kernel as _ConvBiasActFast; the backward is composed of differentiable Functions
-    (activation-derivative kernel, the conv triad), so it can be differentiated again: this is what the
-    real branch of a gradient-penalty step runs.  `s2d` = C when x is the space-to-depth image of a stride-2
-    conv's input (see _DownS2DFast)."""
-
-    @staticmethod
-    def forward(ctx, x, w, bias, residual, stride, pad, lrelu, res_scale, s2d=0):
-        x = _cl(x)
-        if residual is not None:
-            residual = _cl(residual)
-        y = _fwd(x, w, stride, pad, s2d, bias=bias, lrelu=lrelu, residual=residual, res_scale=res_scale)
-        ctx.save_for_backward(x, w, y if lrelu else None)
-        ctx.cfg = (stride, pad, lrelu, float(res_scale) if residual is not None else 1.0, bias is not None,
-                   residual is not None, s2d)
-        return y
+class _ConvBiasActDD(_ConvBiasActFast):
+    """The same forward (inherited) with a backward composed of differentiable Functions (activation-derivative kernel, the
+    conv triad), so it can be differentiated again: this is what the real branch of a gradient-penalty step runs."""
 
     @staticmethod
     def backward(ctx, gy):
         x, w, y = ctx.saved_tensors
-        stride, pad, lrelu, scale, has_bias, has_res, s2d = ctx.cfg
+        launch, lrelu, scale, has_bias, has_res, _ = ctx.epi
         gz = _BiasActBwd.apply(gy, y.detach()) if lrelu else gy
         if scale != 1.0:
             gz = gz * scale
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = _Dgrad.apply(gz, w, tuple(x.shape), stride, pad, s2d)
+            gx = _Dgrad.apply(gz, w, tuple(x.shape), launch)
         if _want_param_grad(ctx, 1):
-            gw = _Wgrad.apply(x, gz, tuple(w.shape), stride, pad, s2d)
+            gw = _Wgrad.apply(x, gz, tuple(w.shape), launch)
         if has_bias and _want_param_grad(ctx, 2):
             # a backward that is not itself recorded (the ordinary loss.backward() of a penalty step) takes the read-only
             # reduction kernel: 2.4x faster than the ATen reduce on the 256^2 tensors (.118 vs .285 ms at B=64)
             gb = _channel_sum(gz) if (not torch.is_grad_enabled() and gz.is_cuda and hb.is_cl(gz)) else gz.sum(dim=(0, 2, 3), dtype=torch.float32)
-        return gx, gw, gb, (gz if has_res and ctx.needs_input_grad[3] else None), None, None, None, None, None
+        return gx, gw, gb, (gz if has_res and ctx.needs_input_grad[3] else None), None, None, None
 
 
 _NAT_NOISE = {}
@@ -804,43 +806,48 @@ class _BlurS2DBwd(torch.autograd.Function):
         return _BlurS2D.apply(ggx)
 
 
-class _DownS2DFast(torch.autograd.Function):
-    """(conv3x3_s2(x) + bias + residual) * res_scale with x given space-to-depth: runs as a 3x3/s1 conv over
-    4C channels on the LDS-halo kernels, structurally-zero taps skipped (exactly the original 9*C work)."""
+def _s2d_eligible(c, h, w, prec):
+    """Does a 3x3 / stride-2 conv over c channels at h x w run as a 3x3 / stride-1 conv over the space-to-depth image of its
+    (blurred) input (LDS-DMA kernels)?  The rule of the fused DiscriminatorBlock's tail and of blur_down."""
+    return prec != hb.F32 and c % 64 == 0 and h % 2 == 0 and w % 2 == 0 and w // 2 >= 16 and h // 2 >= 16
 
-    @staticmethod
-    def forward(ctx, x2, w, bias, residual, res_scale):
-        x2 = _cl(x2)
-        if residual is not None:
-            residual = _cl(residual)
-        n, c = w.shape[0], w.shape[1]
-        wf2, _ = hb.pack_weight_s2d(w)
-        y = hb.conv2d_fwd(x2, None, 1, 1, _PRECISION, bias=bias, residual=residual, res_scale=res_scale, packed=wf2,
-                          w_shape=(n, 4 * c, 3, 3), s2d_c=c)
-        ctx.save_for_backward(x2, w)
-        ctx.cfg = (float(res_scale) if residual is not None else 1.0, bias is not None, residual is not None)
-        return y
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gy):
-        x2, w = ctx.saved_tensors
-        scale, has_bias, has_res = ctx.cfg
-        n, c = w.shape[0], w.shape[1]
-        gz, gb = _grad_prologue(_cl(gy), None, False, scale, has_bias and ctx.needs_input_grad[2])
-        gx2 = gw = None
-        if ctx.needs_input_grad[0]:
-            _, wb2 = hb.pack_weight_s2d(w)
-            gx2 = hb.conv2d_bwd_data(gz, None, tuple(x2.shape), 1, 1, _PRECISION, packed=wb2, w_shape=(n, 4 * c, 3, 3),
-                                     s2d_c=c)
-        if ctx.needs_input_grad[1]:
-            gw = hb.conv2d_bwd_weight_s2d(x2, gz, tuple(w.shape), _PRECISION)
-        return gx2, gw, gb, (gz if has_res and ctx.needs_input_grad[3] else None), None
+def _rgb_extra(dtype):
+    """Zero channels that pad an RGB tensor of this dtype to one 16-byte slot: 8 bf16 or 4 fp32 channels."""
+    return 5 if dtype == torch.bfloat16 else 1
+
+
+# One plain conv call (HipOps.conv2d, .blur_down): zero input channels added, 3 outputs run as 4, even-pixel gather first,
+# route "fused" (_ConvBiasActFast) / "composable" (_ConvBiasActDD) / "triad" (_Conv + torch epilogue), the conv's launch.
+_ConvPlan = collections.namedtuple("_ConvPlan", "extra_in pad_out subsample route launch")
+
+
+def _conv_plan(x_shape, x_dtype, w_shape, stride, pad, prec, fast, blurred=False):
+    """Every decision of one plain conv call, from shapes, the input's dtype (it has been through _act), precision mode,
+    fast_enabled() and the two GEMM switches (read per call: tests toggle them; their only reader on this path).  blurred:
+    the call is blur_down, whose blur can write its output space-to-depth.  In this order, each step seeing the earlier:"""
+    cin, (h, w), n, kernel = x_shape[1], x_shape[2:], w_shape[0], tuple(w_shape[2:])
+    # 1. blur_down over the space-to-depth blur output: the shared rule and, on top of it, this form's own two conditions
+    n_mult_of_4, is_3x3 = n % 4 == 0, kernel == (3, 3)
+    s2d = cin if blurred and (stride, pad) == (2, 1) and n_mult_of_4 and is_3x3 and _s2d_eligible(cin, h, w, prec) else 0
+    # 2. RGB: the vector (16-byte) load paths want whole slots: C_in 3 padded to one, N 3 -> 4.  x_dtype is the mode's
+    #    activation dtype here, so this agrees with _dblock_plan, which asks by the mode
+    extra_in, pad_out = (_rgb_extra(x_dtype) if cin == 3 else 0), n == 3
+    # 3. 1x1 / stride 2 (conv_res): contiguous 1x1 / stride-1 GEMMs over the gathered even pixels
+    subsample = stride == 2 and pad == 0 and kernel == (1, 1) and (cin + extra_in) % 4 == 0
+    stride = 1 if s2d or subsample else stride  # both forms run a stride-1 conv
+    # 4. the fused Functions cannot slice their output: a padded one takes the triad, in the fast mode too
+    route = "triad" if pad_out else "fused" if fast else "composable"
+    # 5. the static half of _gemm_1x1; the fused route keeps the project's own kernel for 1x1 convs
+    gemm = (route != "fused" and not s2d and stride == 1 and pad == 0 and kernel == (1, 1) and prec == hb.BF16_ACT
+            and os.environ.get("STYLEX_RES_GEMM", "1") != "0" and os.environ.get("STYLEX_RES_GEMM_DD", "1") != "0")
+    return _ConvPlan(extra_in, pad_out, subsample, route, _ConvLaunch(stride, pad, s2d, gemm))
 
 
 # The fused DiscriminatorBlock.  How a block runs is decided ONCE, by _dblock_plan in the forward; the backward and the
 # gradient-penalty tangent pass (gp_tangent.py) read the plan and the named saved state, never the environment.  The fused
-# modulated conv above (_modconv_plan, _ModConvSaved, _modconv_forward / _modconv_backward) keeps the same promise.
+# modulated conv (_modconv_plan, _ModConvSaved, _modconv_forward / _modconv_backward) and the plain conv path (_conv_plan,
+# the _ConvLaunch record its nodes pass on, _ConvSaved, _conv_forward / _conv_backward) keep the same promise.
 _DBlockPlan = collections.namedtuple(
     "_DBlockPlan", "prec downsample cin pad extra res_gemm s2d fold_res mask1 mask2 alg wgrad_bias c")
 _DBlockSaved = collections.namedtuple("_DBlockSaved", "x xs y1 y2 xb m1 m2 w_res w1 w2 w3")
@@ -862,11 +869,11 @@ def _dblock_plan(x_shape, x_dtype, x_cuda, w_shapes, downsample, prec, s2d_res_s
     pad, extra = None, 0
     if cin == 3:
         rgb8 = bf16 and x_cuda and x_dtype in (torch.float32, torch.bfloat16) and on("STYLEX_PAD_RGB")
-        pad, extra = ("pad_rgb8", 5) if rgb8 else ("_pad_rgb", 5 if bf16 else 1)
+        pad, extra = ("pad_rgb8" if rgb8 else "_pad_rgb"), _rgb_extra(hb.act_dtype(prec))
     # the 1x1 conv of the residual path is a plain GEMM: hipBLASLt in the bf16 mode (2-3x the generic kernel)
     res_gemm = bf16 and on("STYLEX_RES_GEMM")
     # the stride-2 conv as a 3x3/s1 conv over the space-to-depth image of the blur output (LDS-DMA kernels)
-    s2d = downsample and prec != hb.F32 and n2 % 64 == 0 and h % 2 == 0 and w % 2 == 0 and w // 2 >= 16 and h // 2 >= 16
+    s2d = downsample and _s2d_eligible(n2, h, w, prec)
     # Such blocks take the residual conv as a second K segment of that launch (hb.conv2d_s2d_res_fwd): no GEMM, no bf16
     # `res` tensor written and read back (round 4; STYLEX_RES_FOLD=0 = the separate GEMM).  Only the s2d tail consumes it.
     fold_res = (s2d and res_gemm and (cin + extra) % 8 == 0 and on("STYLEX_RES_FOLD")
@@ -931,15 +938,13 @@ def _dblock_tail(plan, y2, res, w3, b3=None, fold=None):
     if not plan.s2d:
         xb = hb.blur3x3_fwd(y2)
         return hb.conv2d_fwd(xb, w3, 2, 1, prec, bias=b3, residual=res, res_scale=c), xb
-    n = y2.shape[1]
     xb = hb.blur3x3_s2d_fwd(y2)
-    wf2, _ = hb.pack_weight_s2d(w3)
     if fold is None:
-        return hb.conv2d_fwd(xb, None, 1, 1, prec, bias=b3, residual=res, res_scale=c, packed=wf2,
-                             w_shape=(w3.shape[0], 4 * n, 3, 3), s2d_c=n), xb
+        return hb.conv2d_fwd_s2d(xb, w3, prec, bias=b3, residual=res, res_scale=c), xb
     xs, wrp, owner, b_res = fold
     bsum = hb.cached_vector("sum32", lambda a, b: a.float() + b.float(), b3, b_res)
-    return hb.conv2d_s2d_res_fwd(xb, wf2, xs, hb._bf16_matrix(wrp, owner=owner), bsum, w3.shape[0], n, c), xb
+    return hb.conv2d_s2d_res_fwd(xb, hb.pack_weight_s2d(w3)[0], xs, hb._bf16_matrix(wrp, owner=owner), bsum, w3.shape[0],
+                                 y2.shape[1], c), xb
 
 
 def _dblock_forward(x, params, downsample):
@@ -979,11 +984,8 @@ def _dblock_backward(plan, saved, g_out, need):
     w1p, wrp, own1, own_res = _dblock_weights(plan, w1, w_res)
     gw3 = None
     if plan.downsample:
-        n = w2.shape[0]
         if plan.s2d:
-            _, wb2 = hb.pack_weight_s2d(w3, scale=c if alg else None)
-            gxb = hb.conv2d_bwd_data(gz3, None, tuple(xb.shape), 1, 1, prec, packed=wb2, w_shape=(w3.shape[0], 4 * n, 3, 3),
-                                     s2d_c=n)
+            gxb = hb.conv2d_bwd_data_s2d(gz3, w3, tuple(xb.shape), prec, scale=c if alg else None)
         else:
             wb3 = hb.pack_weight(w3, False, True, prec, scale=c)[1] if alg else None
             gxb = hb.conv2d_bwd_data(gz3, w3, tuple(xb.shape), 2, 1, prec, packed=wb3, w_shape=tuple(w3.shape))
@@ -1166,17 +1168,34 @@ def _channel_sum(t, scale=1.0):
 # ------------------------------------------------------------------------------------------
 
 
-def _pad_rgb(x, weight):
-    """RGB tensors have 3 channels; the vector (16-byte) load paths of the kernels want multiples of 4.
-    Zero-pad C_in 3->4 (input + weight) and N 3->4 (weight; the caller slices the output): exact."""
-    n_out = weight.shape[0]
-    if weight.shape[1] == 3:
-        extra = 5 if x.dtype == torch.bfloat16 else 1  # 16-byte slots: 8 bf16 or 4 fp32 channels
-        x = torch.cat([x, x.new_zeros(x.shape[0], extra, x.shape[2], x.shape[3])], dim=1)
-        weight = torch.cat([weight, weight.new_zeros(weight.shape[0], extra, weight.shape[2], weight.shape[3])], dim=1)
-    if n_out == 3:
+def _pad_rgb(x, weight, extra_in, pad_out):
+    """Zero-pad C_in by extra_in (input + weight) and, with pad_out, N 3 -> 4 (weight; the caller slices the output): exact."""
+    if extra_in:
+        x = torch.cat([x, x.new_zeros(x.shape[0], extra_in, x.shape[2], x.shape[3])], dim=1)
+        weight = torch.cat([weight, weight.new_zeros(weight.shape[0], extra_in, weight.shape[2], weight.shape[3])], dim=1)
+    if pad_out:
         weight = torch.cat([weight, weight.new_zeros(1, *weight.shape[1:])], dim=0)
-    return x, weight, n_out
+    return x, weight
+
+
+def _conv_apply(plan, x, weight, bias, residual, lrelu, res_scale):
+    """Prepare the operands the plan names and apply the Function it names; x and residual in the activation dtype."""
+    n_out = weight.shape[0]
+    x, weight = _pad_rgb(x, weight, plan.extra_in, plan.pad_out)
+    if plan.subsample:
+        x = _Subsample2.apply(x)
+    if plan.route != "triad":
+        fn = _ConvBiasActFast if plan.route == "fused" else _ConvBiasActDD
+        return fn.apply(x, weight, bias, residual, plan.launch, lrelu, res_scale)
+    y = _Conv.apply(x, weight, plan.launch)[:, :n_out]
+    if lrelu:
+        assert residual is None
+        return _BiasAct.apply(y, bias)
+    if bias is not None:
+        y = y + bias.view(1, -1, 1, 1)
+    if residual is not None:
+        y = (y + residual) * res_scale
+    return y
 
 
 class HipOps:
@@ -1188,26 +1207,9 @@ class HipOps:
     def conv2d(x, weight, bias=None, stride=1, padding=0, lrelu=False, residual=None, res_scale=1.0):
         """nn.Conv2d (+ LeakyReLU(0.2)) — reference :724-736, :771, :881; with `residual` the block
         merge (conv + bias + residual) * res_scale of :743 is fused into the same kernel."""
-        x, weight, n_out = _pad_rgb(_act(x), weight)
-        residual = _act(residual)
-        padded_out = n_out != weight.shape[0]
-        if stride == 2 and padding == 0 and tuple(weight.shape[2:]) == (1, 1) and x.shape[1] % 4 == 0:
-            # 1x1 / stride 2 (conv_res): contiguous 1x1 / stride-1 GEMMs over the gathered even pixels
-            x, stride = _Subsample2.apply(x), 1
-        if not padded_out:
-            fn = _ConvBiasActFast if fast_enabled() else _ConvBiasActDD
-            return fn.apply(x, weight, bias, residual, stride, padding, lrelu, res_scale)
-        y = _Conv.apply(x, weight, stride, padding)
-        if padded_out:
-            y = y[:, :n_out]
-        if lrelu:
-            assert residual is None
-            return _BiasAct.apply(y, bias)
-        if bias is not None:
-            y = y + bias.view(1, -1, 1, 1)
-        if residual is not None:
-            y = (y + residual) * res_scale
-        return y
+        x = _act(x)
+        plan = _conv_plan(tuple(x.shape), x.dtype, tuple(weight.shape), stride, padding, _PRECISION, fast_enabled())
+        return _conv_apply(plan, x, weight, bias, _act(residual), lrelu, res_scale)
 
     @staticmethod
     def modulated_conv2d(x, style, weight, demod=True, eps=1e-8, coeffs=None):
@@ -1223,7 +1225,8 @@ class HipOps:
             return y
         n_out = weight.shape[0]
         w_run = torch.cat([weight, weight.new_zeros(1, *weight.shape[1:])], dim=0) if n_out == 3 else weight
-        y = _Conv.apply(x * s1[:, :, None, None], w_run, 1, (weight.shape[2] - 1) // 2)
+        plan = _conv_plan(tuple(x.shape), x.dtype, tuple(w_run.shape), 1, (weight.shape[2] - 1) // 2, _PRECISION, False)
+        y = _Conv.apply(x * s1[:, :, None, None], w_run, plan.launch)
         if n_out == 3:
             y = y[:, :3]
         if demod:
@@ -1262,15 +1265,10 @@ class HipOps:
     @staticmethod
     def blur_down(x, weight, bias, residual, res_scale):
         """(conv3x3_s2(blur(x)) + bias + residual) * res_scale — the tail of DiscriminatorBlock (:733-743)."""
-        b, c, h, w = x.shape
-        if (_PRECISION != hb.F32 and c % 64 == 0 and weight.shape[0] % 4 == 0 and h % 2 == 0
-                and w % 2 == 0 and w // 2 >= 16 and h // 2 >= 16 and tuple(weight.shape[2:]) == (3, 3)):
-            x2 = _BlurS2D.apply(_act(x))
-            if fast_enabled():
-                return _DownS2DFast.apply(x2, weight, bias, _act(residual), res_scale)
-            return _ConvBiasActDD.apply(x2, weight, bias, _act(residual), 1, 1, False, res_scale, c)
-        return HipOps.conv2d(HipOps.blur3x3(x), weight, bias, stride=2, padding=1, residual=residual,
-                             res_scale=res_scale)
+        x = _act(x)
+        plan = _conv_plan(tuple(x.shape), x.dtype, tuple(weight.shape), 2, 1, _PRECISION, fast_enabled(), blurred=True)
+        xb = _BlurS2D.apply(x) if plan.launch.s2d else _Blur.apply(x)
+        return _conv_apply(plan, xb, weight, bias, _act(residual), False, res_scale)
 
     @staticmethod
     def rgb_block(x, prev_rgb, style, weight, upsample):

@@ -511,6 +511,46 @@ def test_modconv_backward_follows_the_forward_plan_not_the_environment(monkeypat
         ops.set_fast(prev)
 
 
+def test_conv_double_backward_follows_the_forward_plan_not_the_environment(monkeypatch):
+    """STYLEX_RES_GEMM_DD is read once, when ops.conv2d builds the plan: the nodes that the gradient penalty's two backward
+    passes create take the launch record of their forward, so setting the switch to 0 after the forward changes no bit of
+    the gradients (2x16x8x8, bf16: a 1x1 conv with bias on the GEMM route, then a 3x3 conv with LeakyReLU, composable
+    Functions).  The penalty of a piecewise-linear network does not depend on x: its gradient is None in either run.
+    Not asserted: that a run with the switch off from the start differs.  At this shape (K = 16) hipBLASLt and the
+    project's kernel give the same bits (tools/conv_bits.py: the hashes with STYLEX_RES_GEMM_DD=0 equal the default's)."""
+    import stylex_train as st
+
+    g = torch.Generator().manual_seed(17)
+    x = rounded(torch.randn(2, 16, 8, 8, generator=g), "bf16")
+    w1, b1 = torch.randn(16, 16, 1, 1, generator=g) / 4, torch.randn(16, generator=g)
+    w2 = torch.randn(16, 16, 3, 3, generator=g) / 12
+
+    def grads(dd_forward, dd_backward):
+        """Gradients of x, w1, w2 with the switch at `dd_forward` (None: unset) in the forward and `dd_backward` after it."""
+        monkeypatch.delenv("STYLEX_RES_GEMM_DD", raising=False)
+        if dd_forward is not None:
+            monkeypatch.setenv("STYLEX_RES_GEMM_DD", dd_forward)
+        xd, w1d, b1d, w2d = [t.to(DEV).requires_grad_() for t in (x, w1, b1, w2)]
+        y = ops.conv2d(ops.conv2d(xd, w1d, b1d), w2d, None, 1, 1, lrelu=True)
+        assert "ConvBiasActDD" in type(y.grad_fn).__name__
+        first = y.grad_fn.next_functions[0][0]
+        assert "ConvBiasActDD" in type(first).__name__ and first.epi.launch.gemm is (dd_forward != "0")
+        if dd_backward is not None:
+            monkeypatch.setenv("STYLEX_RES_GEMM_DD", dd_backward)
+        st.gradient_norms(xd, y).mean().backward()
+        return [xd.grad, w1d.grad, w2d.grad]
+
+    ops.set_precision("bf16")
+    prev = ops.set_fast(False)
+    try:
+        untouched, flipped = grads(None, None), grads(None, "0")
+    finally:
+        ops.set_fast(prev)
+    assert untouched[0] is None and flipped[0] is None
+    for name, a, b in zip(("w1", "w2"), untouched[1:], flipped[1:]):
+        assert a is not None and torch.equal(a, b), name
+
+
 @pytest.mark.against_definition
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
 @pytest.mark.parametrize("case", [(3, 12, 12, 9, 9), (5, 64, 64, 24, 40)], ids=["3x12x12x9x9", "5x64x64x24x40"])
