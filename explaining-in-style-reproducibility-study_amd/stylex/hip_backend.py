@@ -2130,6 +2130,7 @@ def chan_norm_bwd(x, gy, g, mean, std, eps, want_params=True):
     lib = _ensure_device(x)
     assert is_cl(x) and is_cl(gy) and x.dtype == gy.dtype and x.shape == gy.shape
     bsz, c, h, w = x.shape
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == bsz * h * w for t in (mean, std))
     sh = _shape(bsz * h * w, c)
     gx = empty_cl(tuple(x.shape), x)
     partial = dgb = None
@@ -2208,6 +2209,9 @@ def linattn_bwd(q, k, v, pre, context, lse, gy, heads):
     q, k, v, strides, sh = _linattn_args(q, k, v, heads)
     assert is_cl(gy) and is_cl(pre) and gy.dtype == q.dtype and gy.shape == q.shape
     b = q.shape[0]
+    # the kernels index the saved fp32 operands as dense [B, heads, 64, 64] / [B, heads, 64]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (context, lse))
+    assert tuple(context.shape) == (b, heads, 64, 64) and tuple(lse.shape) == (b, heads, 64)
     nch = lib.stylex_linattn_chunks(sh)
     dq, dk, dv = (empty_cl(tuple(q.shape), q) for _ in range(3))
     ws = _empty(b * heads * (nch + 1) * 64 * 64 + b * heads * 64, dtype=torch.float32, device=q.device)
