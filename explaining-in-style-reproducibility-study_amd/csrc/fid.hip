@@ -44,12 +44,8 @@ __device__ __forceinline__ float load_px(const void* x, long off) {
     return static_cast<const float*>(x)[off];
 }
 
-// save_image's byte (x * 255 + 0.5 clamped to [0, 255], truncated: two roundings, never one fma) and ToTensor's q / 255 (a
-// true division)
-__device__ __forceinline__ float quantise(float v) {
-    const float t = __fadd_rn(__fmul_rn(v, 255.f), 0.5f);
-    return __fdiv_rn(floorf(fminf(fmaxf(t, 0.f), 255.f)), 255.f);
-}
+// save_image's byte and ToTensor's q / 255: stylex_image_quantise (stylex_internal.h, shared with image_metrics.hip)
+__device__ __forceinline__ float quantise(float v) { return stylex_image_quantise(v); }
 
 template <bool BF16>
 __global__ __launch_bounds__(256) void fid_prep_kernel(const void* __restrict__ x, float* __restrict__ y, int Hi, int Wi, int Ho,

@@ -106,6 +106,16 @@ __device__ __forceinline__ unsigned stylex_sign_bits8(uint4 v) {
     }
     return m;
 }
+
+// The byte of an image file, floor(clamp(v * 255 + 0.5, 0, 255)), as a float, and ToTensor's q / 255 (a true division): the
+// 8-bit quantisation of fid.hip and image_metrics.hip.  v * 255 + 0.5 is ONE fused multiply-add, rounded once: what the
+// compiler has always made of fid.hip's __fadd_rn(__fmul_rn(v, 255.f), 0.5f) (the intrinsics are plain operators under
+// the default contraction; same ISA), now written as the instruction it is.  torch's mul(255).add_(0.5) rounds twice
+// (jpeg_rt.hip's to_byte): the two differ only where v * 255 + 0.5 lies within an fp32 ulp of an integer.
+__device__ __forceinline__ float stylex_image_byte(float v) {
+    return floorf(fminf(fmaxf(fmaf(v, 255.f, 0.5f), 0.f), 255.f));
+}
+__device__ __forceinline__ float stylex_image_quantise(float v) { return __fdiv_rn(stylex_image_byte(v), 255.f); }
 #endif
 // 3x3/s1/p1 bf16 kernel with the input halo resident in LDS (conv_halo.hip)
 int stylex_launch_halo(const ConvKParams& p, hipStream_t s);

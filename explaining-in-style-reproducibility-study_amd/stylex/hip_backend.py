@@ -18,6 +18,7 @@ if _os.environ.get("STYLEX_MIOPEN_ALLOW_BWD_GTC", "0") != "1":
     _os.environ.setdefault("MIOPEN_DEBUG_CONV_IMPLICIT_GEMM_ASM_BWD_GTC_XDLOPS_NHWC", "0")
 
 import atexit
+import collections
 import ctypes
 import os
 import weakref
@@ -212,6 +213,10 @@ SIGNATURES = {
                                           ctypes.c_int64, _c_f, _c_f, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_style_edit_max_k": (ctypes.c_int64, []),
     "stylex_style_edit_levels": (ctypes.c_int, [_c_f] * 9 + [ctypes.c_int64] * 5 + [ctypes.c_float, ctypes.c_void_p]),
+    "stylex_image_pair_stats_tile": (ctypes.c_int64, []),
+    "stylex_image_pair_stats_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64] * 4),
+    "stylex_image_pair_stats": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, _i64p, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "stylex_timing_report": (ctypes.c_int, [ctypes.c_int, _i64p, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }
@@ -1191,6 +1196,58 @@ def fid_prep_u8(x, size=299):
     y = torch.empty((b, 3, int(size), int(size)), dtype=torch.float32, device=x.device)
     _check(lib.stylex_fid_prep_u8(_ptr(x), _ptr(y), _shape(b, h, w, int(size), int(size)), _stream()), "stylex_fid_prep_u8")
     return y
+
+
+ImagePairStats = collections.namedtuple("ImagePairStats", "mae mse psnr ssim")
+
+
+def image_pair_tile():
+    """Output tile extent of the image-pair kernel (window positions per block side)."""
+    return int(load_library().stylex_image_pair_stats_tile())
+
+
+def image_pair_sums(x, y, channels=3, quantise=True):
+    """The raw result of stylex_image_pair_stats: dense fp64 [B, 3] on the device, per image the sum of |d|, the sum of d^2
+    (byte differences with `quantise`) and the sum of SSIM over channels and valid window positions."""
+    lib = _ensure_device(x)
+    _ensure_device(y)
+    channels = int(channels)
+    for t in (x, y):
+        if t.dim() != 4 or t.dtype not in (torch.float32, torch.bfloat16):
+            raise StylexHipError("stylex_image_pair_stats: fp32 or bf16 [B, C, H, W] batches, got %s %s" % (tuple(t.shape), t.dtype))
+    if not 1 <= channels <= 4 or x.shape[1] < channels or y.shape[1] < channels:
+        raise StylexHipError("stylex_image_pair_stats: channels = %d must be in 1..4 and within both operands (%s, %s)"
+                             % (channels, tuple(x.shape), tuple(y.shape)))
+    if x.shape[0] != y.shape[0] or x.shape[2:] != y.shape[2:] or x.device != y.device:
+        raise StylexHipError("stylex_image_pair_stats: operands differ in batch, size or device: %s on %s, %s on %s"
+                             % (tuple(x.shape), x.device, tuple(y.shape), y.device))
+    b, _, h, w = x.shape
+    need = lib.stylex_image_pair_stats_workspace_bytes(b, channels, h, w)
+    if need < 0:
+        raise StylexHipError("stylex_image_pair_stats: unsupported shape %s (H and W must be at least 11, the SSIM window)"
+                             % (tuple(x.shape),))
+    ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
+    out = torch.empty((b, 3), dtype=torch.float64, device=x.device)
+    _check(lib.stylex_image_pair_stats(_ptr(x), _ptr(y), _ptr(out), _shape(b, channels, h, w), _shape(*x.stride()),
+                                       _shape(*y.stride()), int(x.dtype == torch.bfloat16), int(y.dtype == torch.bfloat16),
+                                       int(bool(quantise)), _ptr(ws), need, _stream()), "stylex_image_pair_stats")
+    return out
+
+
+def image_pair_stats(x, y, channels=3, quantise=True):
+    """Two image batches [B, >= channels, H, W] (each fp32 or bf16, any strides; H, W >= 11) -> ImagePairStats(mae, mse, psnr,
+    ssim), fp64 [B] tensors on the device.  quantise: compare the bytes an image file would hold (the rule of fid_prep),
+    else clamp(v, 0, 1).  mae / mse over pixels and channels with data range 1; psnr = 10 log10(1 / mse), inf at mse == 0;
+    ssim: 11 x 11 Gaussian window, sigma 1.5, valid positions, mean over positions and channels."""
+    sums = image_pair_sums(x, y, channels, quantise)
+    b, _, h, w = x.shape
+    n = float(int(channels) * h * w)
+    scale = 255.0 if quantise else 1.0  # byte sums are exact integers: the division happens here, in fp64
+    mae = sums[:, 0] / (scale * n)
+    mse = sums[:, 1] / (scale * scale * n)
+    psnr = torch.where(mse > 0, -10.0 * torch.log10(mse), torch.full_like(mse, float("inf")))
+    ssim = sums[:, 2] / float(int(channels) * (h - 10) * (w - 10))
+    return ImagePairStats(mae, mse, psnr, ssim)
 
 
 def affine_act_slice_fwd(x, scale, shift, out, c0, relu=True):

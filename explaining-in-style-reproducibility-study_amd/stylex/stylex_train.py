@@ -1647,6 +1647,35 @@ class Trainer:
 
     @torch.no_grad()
     @_own_rng_mode
+    def evaluate_reconstruction(self, num_batches, quantise=True):
+        """Reconstruction fidelity on `num_batches` loader batches (recon_metrics.py; the reference has no such report):
+        per image MAE, MSE, PSNR and SSIM of G_EMA(encoder(x), classifier(x)) against x from the fused image-pair kernel
+        (quantise: on the bytes an image file would hold), the LPIPS distance of the Trainer's own network, and the
+        classifier KL, agreement and probability shift.  Returns recon_metrics.summary(...), appends `steps,<json>` to
+        results_dir/name/recon_scores.txt (as fid_scores.txt is appended) and writes the per-image arrays to
+        results_dir/name/recon_<checkpoint number>.npz.  Nothing calls it by default.  Rank 0 only."""
+        if not self.is_main:
+            return None
+        import json
+
+        import recon_metrics
+
+        if self.StylEx is None:
+            self.init_StylEx()
+        ev = recon_metrics.ReconEvaluator(self.StylEx, self.classifier, self.lpips_fn or get_lpips(self.device),
+                                          self.new_architecture, quantise=quantise)
+        for _ in range(num_batches):
+            ev.add(self._next_batch())
+        out = ev.summary()
+        folder = self.results_dir / self.name
+        folder.mkdir(parents=True, exist_ok=True)
+        np.savez(str(folder / f"recon_{self.checkpoint_num}.npz"), **ev.per_image())
+        with open(str(folder / "recon_scores.txt"), "a") as f:
+            f.write(f"{self.steps},{json.dumps(out, sort_keys=True)}\n")
+        return out
+
+    @torch.no_grad()
+    @_own_rng_mode
     def truncate_style(self, tensor, trunc_psi=0.75):
         m = self.StylEx
         if not exists(self.av):

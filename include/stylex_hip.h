@@ -692,6 +692,32 @@ int stylex_style_edit_levels(const float* coords, const float* smin, const float
                              const int32_t* seg_start, float* out, int64_t N, int64_t S, int64_t K, int64_t L, int64_t G,
                              float shift_size, void* stream);
 
+/* ---- image-pair statistics: |d|, d^2 and SSIM sums per image (csrc/image_metrics.hip; stylex/recon_metrics.py) --
+ * How far a reconstruction G(encoder(x), classifier(x)) is from x.  sh = {B, C, H, W}; x, y [B][>= C][H][W], each fp32 or
+ * bf16 (x_is_bf16, y_is_bf16) and each read through its own element strides {b, c, h, w} (non-negative; any layout, a
+ * channel slice included); only channels 0 .. C - 1 are read, 1 <= C <= 4.
+ * Value rule per element: quantise = 1: the byte of stylex_fid_prep, q = floor(clamp(v * 255 + 0.5, 0, 255)), and the
+ * image value q / 255 (a true division); quantise = 0: clamp(v, 0, 1) in fp32.
+ * out dense fp64 [B][3], per image:
+ *   [0] sum over pixels and channels of |d|, [1] of d^2 — d the difference of the BYTES with quantise = 1 (exact integers:
+ *       divide by 255 N and 255^2 N), of the clamped values otherwise (|d| rounded once, d^2 three roundings, fp64 sums);
+ *   [2] sum over channels and the (H - 10) x (W - 10) valid window positions of SSIM (Wang et al. 2004): 11 x 11 Gaussian
+ *       window, sigma 1.5, normalised; population moments E[.] - mu mu; C1 = 0.01^2, C2 = 0.03^2 (data range 1).
+ * One block per (image, channel, T x T output tile), T = stylex_image_pair_stats_tile(): both halo tiles staged once into
+ * LDS, separable horizontal pass of x, y, x^2, y^2, xy into LDS, vertical pass and quotient in registers, fp64 from the
+ * thread outward, one partial per block in the workspace; a second launch adds the partials of an image in fixed order.
+ * No atomics: the same inputs give the same bits.  The three centred moments use the same operation forms, so that
+ * identical operands give a quotient of exactly 1.0f at every position and out[b][2] = C (H - 10) (W - 10) exactly.
+ * workspace: at least stylex_image_pair_stats_workspace_bytes(B, C, H, W) bytes, 8-byte aligned.
+ * STYLEX_EINVAL, before anything is launched: a NULL pointer, B < 1, C outside 1..4, H or W below 11, a negative stride, an
+ * offset or a block count past 2^31 - 1, a workspace that is too small or misaligned.  workspace_bytes returns -1 for
+ * such a shape. */
+int64_t stylex_image_pair_stats_tile(void);
+int64_t stylex_image_pair_stats_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+int stylex_image_pair_stats(const void* x, const void* y, double* out, const int64_t* sh, const int64_t* x_strides,
+                            const int64_t* y_strides, int x_is_bf16, int y_is_bf16, int quantise, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
