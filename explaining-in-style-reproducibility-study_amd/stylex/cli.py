@@ -45,6 +45,7 @@ DEFAULTS = dict(
     precision="fp32",
     fid_weights=None,  # Inception weights of --calculate_fid_every: a path or random:<seed> (fid_inception.resolve_weights)
     fid_jpeg=False,  # generated images of calculate_fid through the reference's JPEG round trip (quality 75) on the device
+    fid_metrics=(),  # beside FID, from the same features: kid and / or pr (--fid_metrics kid,pr) -> fid_metrics.txt
 )
 
 # train_from_folder kwarg -> Trainer kwarg, where the names differ

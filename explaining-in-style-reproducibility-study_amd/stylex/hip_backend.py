@@ -217,6 +217,13 @@ SIGNATURES = {
     "stylex_image_pair_stats_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64] * 4),
     "stylex_image_pair_stats": (ctypes.c_int, [_c_f, _c_f, _c_f, _i64p, _i64p, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "stylex_feat_rownorm": (ctypes.c_int, [_c_f, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "stylex_feat_poly_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64] * 2),
+    "stylex_feat_poly_sum": (ctypes.c_int, [_c_f, _c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                            ctypes.c_double, ctypes.c_double, _c_f, _c_f, ctypes.c_void_p]),
+    "stylex_feat_dist2_block": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f] + [ctypes.c_int64] * 5 + [_c_f, ctypes.c_void_p]),
+    "stylex_feat_row_kth": (ctypes.c_int, [_c_f] + [ctypes.c_int64] * 4 + [_c_f, ctypes.c_void_p]),
+    "stylex_feat_col_any": (ctypes.c_int, [_c_f, _c_f] + [ctypes.c_int64] * 3 + [_c_f, ctypes.c_void_p]),
     "stylex_timing_report": (ctypes.c_int, [ctypes.c_int, _i64p, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }
@@ -1275,6 +1282,90 @@ def fid_moments_acc(x, total, gram):
     _check(lib.stylex_fid_moments_acc(_ptr(x), _ptr(feat), _ptr(total), _ptr(gram), b, d, h * w, _stream()),
            "stylex_fid_moments_acc")
     return feat
+
+
+def _feat_rows(t):
+    """A feature matrix as the pairwise kernels read it: dense fp32 [n, D] on the GPU, D a multiple of 16."""
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() or t.shape[1] < 16 or t.shape[1] % 16:
+        raise StylexHipError("feature metrics: dense fp32 [n, D] rows with D a multiple of 16, got %s %s" % (tuple(t.shape), t.dtype))
+    return t
+
+
+def _f64_out(out, shape, like):
+    return _out_as(out, shape, torch.float64, like)
+
+
+def feat_rownorm(x, out=None):
+    """Squared norms of the rows of x [n, D] in fp64 [n] (stylex_feat_rownorm)."""
+    lib = _ensure_device(x)
+    n, d = _feat_rows(x).shape
+    out = _f64_out(out, (n,), x)
+    _check(lib.stylex_feat_rownorm(_ptr(x), _ptr(out), n, d, _stream()), "stylex_feat_rownorm")
+    return out
+
+
+def feat_poly_tiles(n, m):
+    """Number of fp64 tile sums stylex_feat_poly_sum needs as workspace for n x m pairs."""
+    need = load_library().stylex_feat_poly_workspace_bytes(int(n), int(m))
+    if need < 0:
+        raise StylexHipError("stylex_feat_poly_sum: unsupported extent %d x %d" % (n, m))
+    return need // 8
+
+
+def feat_poly_sum(x, y, symmetric=False, gamma=None, coef0=1.0, out=None, ws=None):
+    """sum over pairs of (x_i . y_j * gamma + coef0)^3 (gamma = 1 / D by default) as one fp64 element on the device; with
+    `symmetric` the pairs i == j are left out (pass the same rows twice).  `out` [1] and `ws` [feat_poly_tiles(n, m)] may be
+    the caller's fp64 buffers (stylex_feat_poly_sum)."""
+    lib = _ensure_device(x)
+    n, d = _feat_rows(x).shape
+    m, dy = _feat_rows(y).shape
+    if d != dy or x.device != y.device:
+        raise StylexHipError("stylex_feat_poly_sum: operands differ in width or device: %s, %s" % (tuple(x.shape), tuple(y.shape)))
+    tiles = feat_poly_tiles(n, m)
+    ws = _f64_out(ws, (tiles,), x)
+    out = _f64_out(out, (1,), x)
+    _check(lib.stylex_feat_poly_sum(_ptr(x), _ptr(y), n, m, d, int(bool(symmetric)), 1.0 / d if gamma is None else float(gamma),
+                                    float(coef0), _ptr(ws), _ptr(out), _stream()), "stylex_feat_poly_sum")
+    return out
+
+
+def feat_dist2_block(x, y, nx, ny, row0, rows, out=None):
+    """Squared distances max(nx_i + ny_j - 2 x_i . y_j, 0) between rows row0 .. row0 + rows - 1 of x and all rows of y, fp64
+    [rows, m]; nx, ny from feat_rownorm (stylex_feat_dist2_block)."""
+    lib = _ensure_device(x)
+    n, d = _feat_rows(x).shape
+    m, dy = _feat_rows(y).shape
+    if d != dy or tuple(nx.shape) != (n,) or tuple(ny.shape) != (m,) or nx.dtype != torch.float64 or ny.dtype != torch.float64:
+        raise StylexHipError("stylex_feat_dist2_block: x %s, y %s, nx %s, ny %s do not fit" % (tuple(x.shape), tuple(y.shape),
+                                                                                             tuple(nx.shape), tuple(ny.shape)))
+    assert nx.is_contiguous() and ny.is_contiguous() and nx.device == ny.device == x.device == y.device
+    out = _f64_out(out, (int(rows), m), x)
+    _check(lib.stylex_feat_dist2_block(_ptr(x), _ptr(y), _ptr(nx), _ptr(ny), int(row0), int(rows), n, m, d, _ptr(out), _stream()),
+           "stylex_feat_dist2_block")
+    return out
+
+
+def feat_row_kth(block, k, self0=-1, out=None):
+    """The k-th smallest entry (1 <= k <= 8) of every row of the fp64 block [R, M]; with self0 >= 0 column self0 + i is left
+    out of row i (stylex_feat_row_kth)."""
+    lib = _ensure_device(block)
+    assert block.dim() == 2 and block.dtype == torch.float64 and block.is_contiguous(), (tuple(block.shape), block.dtype)
+    r, m = block.shape
+    out = _f64_out(out, (r,), block)
+    _check(lib.stylex_feat_row_kth(_ptr(block), r, m, int(k), int(self0), _ptr(out), _stream()), "stylex_feat_row_kth")
+    return out
+
+
+def feat_col_any(block, r2, row0, flags):
+    """flags[j] |= any_i block[i][j] <= r2[row0 + i] for the fp64 block [R, M]; flags uint8 [M], updated in place
+    (stylex_feat_col_any)."""
+    lib = _ensure_device(block)
+    assert block.dim() == 2 and block.dtype == torch.float64 and block.is_contiguous(), (tuple(block.shape), block.dtype)
+    r, m = block.shape
+    assert r2.dtype == torch.float64 and r2.dim() == 1 and r2.is_contiguous() and int(row0) >= 0 and int(row0) + r <= r2.shape[0]
+    assert flags.dtype == torch.uint8 and tuple(flags.shape) == (m,) and flags.is_contiguous() and flags.device == block.device
+    _check(lib.stylex_feat_col_any(_ptr(block), _ptr(r2), int(row0), r, m, _ptr(flags), _stream()), "stylex_feat_col_any")
+    return flags
 
 
 def relu_gate_add(a, b, y, out=None):

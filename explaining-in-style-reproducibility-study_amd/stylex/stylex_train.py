@@ -652,7 +652,7 @@ class Trainer:
                  # --- extensions (defaults reproduce the reference) ---
                  classifier=None, lpips_fn=None, gp_every=4, pl_every=32, pl_after=5000, device=None,
                  save_training_state=False, graphs=None, graph_warmup=4, new_architecture=False, device_pipeline=None,
-                 device_rng=None, fid_weights=None, fid_jpeg=False, *args, **kwargs):
+                 device_rng=None, fid_weights=None, fid_jpeg=False, fid_metrics=(), *args, **kwargs):
         kl_rec_during_disc = kwargs.pop("kl_rec_during_disc", False)  # cli.py forwards it; only the new architecture reads it
         # new_architecture = the conditional-D variant the reference ships as stylex_train_new.py (cli.py:17-22)
         self.new_architecture = bool(new_architecture)
@@ -723,6 +723,13 @@ class Trainer:
         # fid_jpeg: the generated images of calculate_fid go through the JPEG round trip of the reference's .jpg files
         # (quality 75) on the device; nothing changes for transparent models, whose image_extension is png
         self.fid_jpeg = bool(fid_jpeg)
+        # fid_metrics: what calculate_fid computes beside FID from the same pooled features: "kid" (kernel inception
+        # distance) and / or "pr" (improved precision and recall); a tuple, a list or "kid,pr".  Empty: nothing changes
+        if isinstance(fid_metrics, str):
+            fid_metrics = [v for v in fid_metrics.split(",") if v]
+        self.fid_metrics = tuple(fid_metrics or ())
+        assert set(self.fid_metrics) <= {"kid", "pr"}, "fid_metrics takes kid and pr, got %r" % (self.fid_metrics,)
+        self.last_fid_metrics = None
         self.is_ddp, self.is_main, self.rank, self.world_size = is_ddp, rank == 0, rank, world_size
         self.sample_from_encoder = sample_from_encoder
         self.logger = None
@@ -1372,6 +1379,11 @@ class Trainer:
                 self.last_fid = self.calculate_fid(math.ceil(self.calculate_fid_num_images / self.batch_size))
                 with open(str(self.results_dir / self.name / "fid_scores.txt"), "a") as f:  # reference :1500-1503
                     f.write(f"{self.steps},{self.last_fid}\n")
+                if self.fid_metrics:  # steps,fid,kid_mean,kid_std,precision,recall; a metric that was not asked for stays empty
+                    got = self.last_fid_metrics
+                    cells = [self.steps, self.last_fid, *got.get("kid", ("", "")), got.get("precision", ""), got.get("recall", "")]
+                    with open(str(self.results_dir / self.name / "fid_metrics.txt"), "a") as f:
+                        f.write(",".join(str(c) for c in cells) + "\n")
         self.steps += 1
         self.av = None
 
@@ -1612,7 +1624,12 @@ class Trainer:
         4:2:0), and the reals as PNG.  With fid_jpeg=True the generated batches go through that JPEG round trip on the
         device (hip_backend.jpeg_roundtrip: the bytes Pillow would decode, no file) — the setting whose numbers compare
         with the reference's fid_scores.txt; the reals and transparent models (.png) stay lossless.  With the default
-        fid_jpeg=False the generated images are quantised to 8 bits only."""
+        fid_jpeg=False the generated images are quantised to 8 bits only.
+        With fid_metrics the evaluator keeps the pooled features it already computes, and KID and / or precision and recall
+        of the same two sets (fid.kid, fid.precision_recall) are left in last_fid_metrics; the real features
+        are cached beside the statistics (real_features.npy and its tag).  The returned FID, the loader batches and the
+        random draws consumed are those of fid_metrics=() (KID draws its subsets from a generator of its own) — except that
+        statistics cached by a run without the features are computed again, once, together with them."""
         if not self.is_main:
             return None
         import fid
@@ -1620,15 +1637,24 @@ class Trainer:
 
         m = self.StylEx
         if self._fid_eval is None:
-            self._fid_eval = fid.FIDEvaluator(fid_inception.build(self.fid_weights, self.device))
+            self._fid_eval = fid.FIDEvaluator(fid_inception.build(self.fid_weights, self.device),
+                                              keep_features=bool(self.fid_metrics))
         ev = self._fid_eval
         tag = "image_size=%d;weights=%s" % (self.image_size, ev.net.weights_id)
-        cache = self.fid_dir / "real_stats.npz"
+        cache, feature_cache = self.fid_dir / "real_stats.npz", self.fid_dir / "real_features.npy"
         ev.real = None if self.clear_fid_cache else fid.FIDStats.load(cache, tag, self.device)
+        if ev.real is not None and ev.keep_features:
+            feats = fid.load_features(feature_cache, tag, self.device)
+            if feats is None or feats.shape[0] != ev.real.n:
+                ev.real = None  # statistics without their features: both are made again
+            else:
+                ev.set_real_features(feats)
         if ev.real is None:
             for _ in range(num_batches):
                 ev.add_real(self._next_batch())
             ev.real.save(cache, tag)
+            if ev.keep_features:
+                fid.save_features(feature_cache, ev.real_features, tag)
         ev.fake = None
         jpeg_quality = 75 if self.fid_jpeg and self.image_extension == "jpg" else None  # Pillow's default quality
         m.eval()
@@ -1643,7 +1669,15 @@ class Trainer:
                 probs = probs / torch.sum(probs, dim=1, keepdim=True)
             ev.add_fake(self.generate_truncated(m.SE, m.GE, latents, n, trunc_psi=self.trunc_psi, probabilities=probs),
                         jpeg_quality=jpeg_quality)
-        return ev.value()
+        value = ev.value()
+        if self.fid_metrics:
+            got = {}
+            if "kid" in self.fid_metrics:
+                got["kid"] = ev.kid()
+            if "pr" in self.fid_metrics:
+                got["precision"], got["recall"] = ev.precision_recall()
+            self.last_fid_metrics = got
+        return value
 
     @torch.no_grad()
     @_own_rng_mode

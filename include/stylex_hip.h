@@ -718,6 +718,33 @@ int stylex_image_pair_stats(const void* x, const void* y, double* out, const int
                             const int64_t* y_strides, int x_is_bf16, int y_is_bf16, int quantise, void* workspace,
                             int64_t workspace_bytes, void* stream);
 
+/* ---- pairwise feature metrics: KID and improved precision / recall (csrc/feature_metrics.hip; stylex/fid.py) ---
+ * x [n][D], y [m][D]: dense fp32 feature rows, 16-byte aligned, read as fp64; D >= 16 and D % 16 == 0.  Dot products are
+ * accumulated in fp64 on v_mfma_f64_16x16x4_f64, one wave per 16 x 16 tile of pairs, D ascending in blocks of 16.  No
+ * atomics: the same inputs give the same bits.  Every fp64 buffer is 8-byte aligned.
+ *   stylex_feat_rownorm      out[i] = sum_k x[i][k]^2.
+ *   stylex_feat_poly_sum     out[0] = sum over pairs (i, j) of (x_i . y_j * gamma + coef0)^3, without the pairs i == j when
+ *                            `symmetric` (then n == m; pass the same rows twice).  Each tile's sum goes to tile_sums_ws
+ *                            (stylex_feat_poly_workspace_bytes(n, m) bytes), a second launch adds them in one fixed order.
+ *   stylex_feat_dist2_block  out_block[i][j] = max(nx[row0 + i] + ny[j] - 2 x_{row0 + i} . y_j, 0), dense fp64 [R][m], for
+ *                            the R rows of x from row0 (row0 + R <= n); nx [n], ny [m] from stylex_feat_rownorm.
+ *   stylex_feat_row_kth      out_r2[i] = the k-th smallest of block[i][.] (dense fp64 [R][M]), 1 <= k <= 8; with self0 >= 0
+ *                            column self0 + i is left out of row i (by index: equal values elsewhere count).
+ *   stylex_feat_col_any      flags[j] |= any_i block[i][j] <= r2[row0 + i]; flags: M bytes, 0 or 1, each owned by one thread
+ *                            per launch, so successive launches on one stream combine row blocks.
+ * STYLEX_EINVAL, before anything is launched: a null pointer, D < 16 or D % 16 != 0, a size below 1, a row range outside
+ * x, k outside 1..8, fewer than k columns besides the one left out (k >= n for a symmetric block), symmetric with n != m,
+ * a misaligned buffer, an extent or product (n D, m D, R m, tile count) past 2^31 - 1.  workspace_bytes returns -1 then. */
+int stylex_feat_rownorm(const float* x, double* out, int64_t n, int64_t D, void* stream);
+int64_t stylex_feat_poly_workspace_bytes(int64_t n, int64_t m);
+int stylex_feat_poly_sum(const float* x, const float* y, int64_t n, int64_t m, int64_t D, int symmetric, double gamma, double coef0,
+                         double* tile_sums_ws, double* out, void* stream);
+int stylex_feat_dist2_block(const float* x, const float* y, const double* nx, const double* ny, int64_t row0, int64_t R, int64_t n,
+                            int64_t m, int64_t D, double* out_block, void* stream);
+int stylex_feat_row_kth(const double* block, int64_t R, int64_t M, int64_t k, int64_t self0, double* out_r2, void* stream);
+int stylex_feat_col_any(const double* block, const double* r2, int64_t row0, int64_t R, int64_t M, unsigned char* flags,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
